@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- MPC steps/s of the TZDDPC hot path on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W [--config NAME] [--repeats R]
+  python bench.py --gpus N --steps K --warmup W [--config NAME] [--repeats R] [--full] [--dump-outputs DIR]
   python bench.py -m TZDDPC|STZDDPC -ho HORIZON [-k0 K0] [-n NEVALS]     (flags of the reference's complexity harness,
                                                                            examples/1.double_integrator_computation_complexity.py:179-189)
 
@@ -23,8 +23,15 @@ steps run again untimed): `value` is the MEDIAN window, the spread is reported b
 example's single input) and dim5m2_n20 (config 4 as BASELINE.json states it: two inputs), di_n5 / di_n10 / di_n40 / di_n80 and the
 simplified di_n20_k1 / di_n20_k2 (config 5); genstack_dim5_k1 times kernel K1g (literal stacked-generator tubes).
 
-Beside the driver-contract window the line carries `full_run` (SURVEY 8d's metric as written: T_sim = 50 closed-loop steps from X0,
-nothing untimed) and `jittered_start` (every trajectory from its own point of X0 +- 0.25, seed 7).
+A plain run does only what the headline needs: set-up, warm-up, the timed windows, the result line.  With --full the line also
+carries `full_run` (SURVEY 8d's metric as written: T_sim = 50 closed-loop steps from X0, nothing untimed), `jittered_start` (every
+trajectory from its own point of X0 +- 0.25, seed 7) and `cpu_baseline` (the plain-C oracle on the host); for
+the K1g configurations, `max_err_vs_numpy`.
+
+--dump-outputs DIR writes what the timed path computed in its last step (the last timed window of the headline) as DIR/<name>.npy in
+float64: per trajectory the final state `x`, nominal state `xbar`, error `e`, last applied input `u`, last stage cost `cost` and the
+sticky `status` (for K1g: the interval centres `c` and radii `rx` / `ru` of every tube).  Above 64 MB in all, the same fixed, seeded
+sample of trajectories is written from every array, its indices in `sample_rows.npy`.
 """
 import argparse
 import json
@@ -238,16 +245,27 @@ def cpu_baseline(ctl, A, B, zon, label, warmup, steps, full_steps=0, seconds_bud
 
 
 def ensure_built():
-    """Build (or confirm current: content hash of sources and flags) the in-tree libraries, one rank at a time."""
+    """Build (or confirm current: content hash of sources and flags) the in-tree libraries, one rank at a time.  The tree may be
+    read-only to the process that benchmarks it: confirming current libraries writes nothing, and flock needs no write access."""
     import fcntl
-    os.makedirs(os.path.join(ROOT, "tzddpc_amd", "lib"), exist_ok=True)
-    with open(os.path.join(ROOT, "tzddpc_amd", "lib", ".build.lock"), "w") as lk:
-        fcntl.flock(lk, fcntl.LOCK_EX)
+    lock = os.path.join(ROOT, "tzddpc_amd", "lib", ".build.lock")
+    lk = None
+    for mode in ("a", "r"):
         try:
-            import __graft_entry__
-            __graft_entry__.build()
-        finally:
+            os.makedirs(os.path.dirname(lock), exist_ok=True)
+            lk = open(lock, mode)
+            break
+        except OSError:
+            pass
+    try:
+        if lk is not None:                     # no lock file and no right to create one: nobody can rebuild this tree
+            fcntl.flock(lk, fcntl.LOCK_EX)
+        import __graft_entry__
+        __graft_entry__.build()
+    finally:
+        if lk is not None:
             fcntl.flock(lk, fcntl.LOCK_UN)
+            lk.close()
 
 
 def archived_traffic(config, nz, mi, Bl, K):
@@ -267,6 +285,27 @@ def archived_traffic(config, nz, mi, Bl, K):
         return None, None
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, cap_bytes=DUMP_CAP_BYTES):
+    """Write `arrays` (name -> array whose first axis is the trajectory) as dirname/<name>.npy in float64.  Above `cap_bytes` in all,
+    the same fixed, seeded sample of trajectories is taken from every array and its indices are written as sample_rows.npy."""
+    arrays = {k: np.ascontiguousarray(np.asarray(v, dtype=np.float64)) for k, v in arrays.items()}
+    rows = {a.shape[0] for a in arrays.values()}
+    assert len(rows) == 1, "every dumped array has one row per trajectory"
+    rows = rows.pop()
+    per_row = sum(a.nbytes for a in arrays.values()) / max(rows, 1)
+    if per_row * rows > cap_bytes:
+        keep = max(1, int(cap_bytes // (per_row + 8)))
+        idx = np.sort(np.random.default_rng(0).choice(rows, keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["sample_rows"] = idx.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -276,8 +315,10 @@ def parse_args(argv=None):
     ap.add_argument("--batch", type=int, default=0, help="trajectories per GPU (default: the configuration's)")
     ap.add_argument("-ho", "--horizon", type=int, default=0, help="override the configuration's horizon (reference harness: -ho)")
     ap.add_argument("--repeats", type=int, default=0, help="timed windows (median reported; default 11)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--full-run-steps", type=int, default=50, help="T_sim of the untimed-nothing run from X0 (SURVEY 8d); 0 = skip")
+    ap.add_argument("--full", action="store_true", help="also the legs beyond the headline: full_run, jittered_start, cpu_baseline (K1g: the numpy check)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the timed path computed in its last step as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--full-run-steps", type=int, default=50, help="with --full: T_sim of the untimed-nothing run from X0 (SURVEY 8d); 0 = skip")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="gloo only with --dry-run")
     ap.add_argument("--dry-run", action="store_true", help="launch / shard / gather logic only (no GPU): CPU rehearsal of --gpus N")
     # flags of the reference's complexity harness (examples/1.double_integrator_computation_complexity.py:179-189)
@@ -369,6 +410,8 @@ def dry_run(args):
         per_rank = [float(t.item()) for t in tl]
     if rank == 0:
         full = results(0, total)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"result": gathered.numpy()})
         print(json.dumps({"metric": "dry run (launch / shard / gather logic only)", "value": None, "unit": "MPC steps/s", "n_gpus": world, "steps": K,
                           "warmup": args.warmup, "dry_run": True, "backend": args.backend, "scaling": "weak",
                           "world_size_read_back": dist.get_world_size() if use_dist else 1,
@@ -414,9 +457,13 @@ def bench_genstack(args, local_rank=0):
     ms = [call() for _ in range(args.steps)]                  # HIP events inside the library around the streaming kernel
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    ref = evaluate_host(st, e0[B // 2], zeta[B // 2])
-    err = max(np.abs(rx[B // 2].cpu().numpy() - np.array([r[1] for r in ref])).max() / (1 + max(r[1].max() for r in ref)),
-              np.abs(c[B // 2].cpu().numpy() - np.array([r[0] for r in ref])).max())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"c": c.cpu().numpy(), "rx": rx.cpu().numpy(), "ru": ru.cpu().numpy()})
+    check = {}
+    if args.full:
+        ref = evaluate_host(st, e0[B // 2], zeta[B // 2])
+        check["max_err_vs_numpy"] = float(max(np.abs(rx[B // 2].cpu().numpy() - np.array([r[1] for r in ref])).max() / (1 + max(r[1].max() for r in ref)),
+                                              np.abs(c[B // 2].cpu().numpy() - np.array([r[0] for r in ref])).max()))
     med = float(np.median(ms))
     tiles = (B + 255) // 256
     bytes_alg = info["stack_bytes"] * tiles + B * (n + N * (n + m)) * 8 + info["chunks"] * B * (n + m) * 8
@@ -444,7 +491,7 @@ def bench_genstack(args, local_rank=0):
                       "config": {"workload": f"{desc}; {sysname} n={n} m={m}, N={N}, k0={k0}, {info['generators']} generators ({info['stack_bytes'] / 1e6:.1f} MB), {B} trajectories",
                                  "name": args.config, "generators": info["generators"], "max_generators_per_tube": int(st.num_generators.max()),
                                  "chunks": info["chunks"], "trajectories": B, "stack_build_s": t_build},
-                      "roofline": roof, "max_err_vs_numpy": float(err)}))
+                      "roofline": roof, **check}))
     return 0
 
 
@@ -506,9 +553,9 @@ def main(argv=None):
     lo, hi = shard_range(total, world, rank)
     assert hi - lo == Bl
     K, W, R = args.steps, args.warmup, max(1, args.repeats)
-    Tfull = max(0, args.full_run_steps)
+    Tfull = max(0, args.full_run_steps) if args.full else 0
     Wv = zon.W.compute_vertices()
-    nsteps = max(K + W, Tfull)
+    nsteps = max(K + W, max(0, args.full_run_steps))                     # the same noise array with and without --full
     noise = torch.from_numpy(np.ascontiguousarray(vertex_noise(Wv, lo, Bl, nsteps).transpose(1, 0, 2))).to(dev)   # steps x B x n
     x_same = torch.from_numpy(np.tile(zon.X0.center, (Bl, 1))).to(dev)
     # "x0 = X0 center for all (optionally + box jitter +-0.25, seed 7)": drawn for the whole job, sliced per rank
@@ -598,6 +645,11 @@ def main(argv=None):
                                                                          # windows of this size (0.63 -> 0.585 ms kernel time, profiles/r4_window_trend.txt)
     head = measure(x_same, W, K, R, DISCARD)                             # (clocks, instruction / constant caches); then the driver-contract window:
                                                                          # W untimed steps from X0, then K timed, R times from a fresh start
+    outputs = None
+    if args.dump_outputs:                                                # what the last timed window left, before any other leg runs
+        state = {"x": x, "xbar": xbar, "e": e, "u": u, "cost": cost, "status": status}
+        outputs = {k: gather_results(t.to(torch.float64).reshape(Bl, -1), total).cpu().numpy().reshape((total,) + tuple(t.shape[1:]))
+                   for k, t in state.items()}
     extra = {}
     if Tfull > 0:
         # SURVEY 8d's metric as written: B * T_sim / wall, T_sim = 50 from X0 with NOTHING untimed (the reference times build + all
@@ -669,7 +721,7 @@ def main(argv=None):
         if tb is not None:
             line["roofline"]["traffic"] = tb
             line["roofline"]["traffic_source"] = tinfo
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 line["cpu_baseline"] = cb = cpu_baseline(ctl, A, Bm, zon, label, W, K, full_steps=Tfull)
                 if cb.get("value"):                       # ratios against the BEST point of the CPU curve; never a quality claim (the roofline is)
@@ -679,6 +731,8 @@ def main(argv=None):
                     cb["full_run"]["gpu_over_cpu"] = line["full_run"]["value"] / cb["full_run"]["value"]
             except Exception as ex:  # the baseline is a report, never a reason to lose the GPU number
                 line["cpu_baseline"] = {"value": None, "unit": "MPC steps/s", "cores": 0, "kind": "port", "sample": f"failed: {ex}"}
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
         print(json.dumps(line))
     if use_dist:
         dist.destroy_process_group()

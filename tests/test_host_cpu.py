@@ -317,6 +317,63 @@ def test_bench_accepts_the_reference_harness_flags():
         bench.parse_args(["--backend", "gloo"])                                    # gloo only as the CPU rehearsal (--dry-run)
 
 
+def test_bench_full_and_dump_outputs(tmp_path):
+    """--full is off by default; --dump-outputs DIR writes one float64 .npy per output with a row per trajectory, the same seeded
+    sample of rows from every array when the total passes the cap, and (CPU rehearsal of --gpus 2) the gathered rows of the job."""
+    import json
+    root = common.__file__.rsplit("/tests/", 1)[0]
+    sys.path.insert(0, root)
+    import bench
+    a = bench.parse_args([])
+    assert a.full is False and a.dump_outputs is None
+    a = bench.parse_args(["--full", "--dump-outputs", str(tmp_path)])
+    assert a.full is True and a.dump_outputs == str(tmp_path)
+    x, st = np.arange(600.0).reshape(100, 3, 2), np.arange(100, dtype=np.int32)
+    bench.dump_outputs(str(tmp_path / "all"), {"x": x, "status": st})
+    got = np.load(tmp_path / "all" / "x.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, x) and np.array_equal(np.load(tmp_path / "all" / "status.npy"), st)
+    assert not (tmp_path / "all" / "sample_rows.npy").exists()
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), {"x": x, "status": st}, cap_bytes=2000)
+    rows = np.load(tmp_path / "s1" / "sample_rows.npy").astype(int)
+    sx, ss = np.load(tmp_path / "s1" / "x.npy"), np.load(tmp_path / "s1" / "status.npy")
+    assert 0 < len(rows) < 100 and sx.nbytes + ss.nbytes + rows.size * 8 <= 2000
+    assert np.array_equal(sx, x[rows]) and np.array_equal(ss, st[rows])
+    assert np.array_equal(np.load(tmp_path / "s2" / "sample_rows.npy"), rows.astype(np.float64))    # fixed seed: the same sample
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--batch", "7", "--dry-run", "--backend", "gloo",
+                        "--dump-outputs", str(tmp_path / "dry")], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    ln = [json.loads(s) for s in p.stdout.splitlines() if s.startswith("{")][0]
+    res = np.load(tmp_path / "dry" / "result.npy")
+    assert res.dtype == np.float64 and res.shape[0] == ln["config"]["gathered_rows"] == 14
+
+
+def test_bench_ensure_built_in_a_read_only_tree(tmp_path, monkeypatch):
+    """The benchmark may run as a user who cannot write to the tree build() left behind: confirming that the libraries are current
+    needs no write access, whether the lock file is missing or belongs to someone else."""
+    root = common.__file__.rsplit("/tests/", 1)[0]
+    sys.path.insert(0, root)
+    import __graft_entry__
+    import bench
+    calls = []
+    monkeypatch.setattr(__graft_entry__, "build", lambda: calls.append(1))
+    monkeypatch.setattr(bench, "ROOT", str(tmp_path))
+    lib = tmp_path / "tzddpc_amd" / "lib"
+    lib.mkdir(parents=True)
+    try:
+        lib.chmod(0o555)
+        bench.ensure_built()                                                        # no lock file, and none can be created
+        lib.chmod(0o755)
+        (lib / ".build.lock").write_text("")
+        (lib / ".build.lock").chmod(0o444)
+        lib.chmod(0o555)
+        bench.ensure_built()                                                        # a lock file this process may only read
+    finally:
+        lib.chmod(0o755)
+    assert calls == [1, 1]
+
+
 def test_zonotope_polygon_matches_the_vertex_enumeration():
     """``Z.reduce(order).polygon`` of the reference's plots (examples/1.double_integrator_sim.py:170,174): boundary of a 2-D zonotope,
     counter-clockwise, equal as a set to the hull of the 2^g enumerated points."""

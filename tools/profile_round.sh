@@ -6,7 +6,7 @@
 tag=${1:-rXX}; cfg=${2:-di_n20}; steps=${3:-20}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 out=gpurun_out; t=${tag}_${cfg}
-python3 bench.py --config $cfg --steps $steps --warmup 5 > $out/${t}_bench.json 2> $out/${t}_bench.err || exit 1
+python3 bench.py --config $cfg --steps $steps --warmup 5 --full > $out/${t}_bench.json 2> $out/${t}_bench.err || exit 1
 B="python3 bench.py --config $cfg --steps $steps --warmup 5 --repeats 1 --no-cpu-baseline --full-run-steps 0"   # no full-run / jitter legs: the timed window is the LAST launch
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/${t}_trace -o t -- $B > $out/${t}_trace.log 2>&1 || exit 1
 cp $(find $out/${t}_trace -name "*kernel_stats.csv" | head -1) $out/${t}_kernel_stats.csv
