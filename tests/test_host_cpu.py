@@ -102,6 +102,33 @@ def test_header_symbols_are_exported(built):
     assert L.tz_abi_version() == native.TZ_ABI_VERSION
 
 
+def test_plan_flags_of_header_and_binding_agree():
+    from tzddpc_amd import native
+    hdr = open(os.path.join(common.__file__.rsplit("/tests/", 1)[0], "include", "tzddpc.h")).read()
+    flags = {"TZ_PLAN_" + k: int(v) for k, v in re.findall(r"^\s*TZ_PLAN_(\w+)\s*=\s*(\d+)", hdr, flags=re.M)}
+    assert flags == {k: v for k, v in vars(native).items() if k.startswith("TZ_PLAN_")}
+    assert flags == {"TZ_PLAN_UNFUSED": 1, "TZ_PLAN_ITEM_GRAM": 4, "TZ_PLAN_NO_STAIRCASE": 8}
+
+
+def test_unknown_plan_flags_are_refused(built):
+    """tz_problem_create refuses plan_flags bits it does not know, among the argument checks that come before any device query."""
+    from tzddpc_amd import native
+    ctl, qp, _ = common.identified_qp("di_n5")
+    for bad in (2, 16, native.TZ_PLAN_UNFUSED | 64):
+        with pytest.raises(native.NativeError, match="plan_flags"):
+            ctl._native_from_qp(qp, {"plan_flags": bad})
+
+
+def test_libraries_read_no_environment(built):
+    """Neither the release nor the diagnostic library imports getenv / secure_getenv: what a caller may choose goes through the
+    problem description and the tz_problem_set_* entry points."""
+    import __graft_entry__ as g
+    for lib in (g.HIP_LIB, g.HIP_LIB_PROF):
+        und = subprocess.run(["nm", "-D", "--undefined-only", lib], stdout=subprocess.PIPE, text=True, check=True).stdout
+        names = {ln.split()[-1].split("@")[0] for ln in und.splitlines() if ln.strip()}
+        assert names and not names & {"getenv", "secure_getenv"}, (lib, names & {"getenv", "secure_getenv"})
+
+
 def test_product_fails_loudly_without_gpu(built):
     """No CPU fallback: on a box without a HIP device problem creation raises (skipped where a GPU exists)."""
     from tzddpc_amd import native

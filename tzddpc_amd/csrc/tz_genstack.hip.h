@@ -27,7 +27,8 @@
 #define TZ_GS_GWDIV 16           // narrow kernel: a wave tile is 1 / TZ_GS_GWDIV of the shared tile; smaller tiles = fewer registers and less LDS = more
                                  // waves per SIMD to cover the LDS latency of the A reads (32 trajectories: 4 -> 0.0624 ms, 8 -> 0.0592, 16 -> 0.0587)
 #endif
-#define TZ_GS_MAXSUB 8           // matrix-core kernel, few trajectories: at most this many blocks share a chunk
+#define TZ_GS_NARROW_SUB 2       // narrow kernel (few trajectories): blocks that share a chunk, each streaming its tiles once (measured at 32
+                                 // trajectories, 636 chunks: 1 -> 0.0670 ms, 2 -> 0.0641 ms, 4 -> 0.120 ms: the un-overlapped prologue of short blocks)
 
 struct GsChunk { int seg, src, g0, g1; };        // generators [g0, g1) of the SORTED stack: tube seg, source src (-1 none, 0 e0, 1 + j zeta_j)
 
@@ -133,14 +134,13 @@ __global__ __launch_bounds__(256) void tz_genstack_kernel(GenstackParams q) {
 //   * the stack is laid out by the host exactly as the LDS tile ([group of 4 generators][component][generator][inner] then the
 //     m0 block), streamed global -> registers -> LDS double-buffered: the loads of tile t + 1 are in flight while tile t is
 //     multiplied, ONE barrier per tile;
-//   * SPLIT = false: a workgroup covers 256 trajectories (wave w: 64 w .. 64 w + 63, NQ = 4 groups of 16) and every wave walks all
-//     generators of the chunk; SPLIT = true (few trajectories: the stack is streamed once, the HBM-bound regime): all four waves
-//     take the same <= 64 trajectories and every fourth group of generators each, partial sums meet in LDS in wave order;
+//   * a workgroup covers 256 trajectories (wave w: 64 w .. 64 w + 63, NQ = 4 groups of 16) and every wave walks all generators of
+//     the chunk; few trajectories (the stack is streamed once, the HBM-bound regime) go to tz_genstack_mfma_narrow_kernel below;
 //   * blockIdx -> (chunk, trajectory tile) so that the tiles of one chunk run on the same XCD (shared L2) back to back.
 struct GsChunkM { int seg, src, q0, nq; };       // groups [q0, q0 + nq) of 4 generators each (zero-padded), tube seg, source src
 
 struct GenstackMParams {
-  int B, n, m, N, nchunk, ntt, nsub;             // ntt = blocks per chunk: trajectory tiles of 256, or (SPLIT) nsub sub-ranges of its tiles
+  int B, n, m, N, nchunk, ntt, nsub;             // ntt = blocks per chunk: trajectory tiles of 256, or (narrow kernel) nsub sub-ranges of its tiles
   const double* recs;                            // groups of GD = 4 R (P + 1) doubles (R = P: K rows appended by the host; R = n: formed in the kernel)
   const double* K;                               // m x n (used when R < P)
   const GsChunkM* chunks;
@@ -159,7 +159,7 @@ template <int R, int P> struct GsTile {
 // R stored rows per generator, inner dimension P = n + m.  R = P: the m rows K M, K m0 come appended from the host.  R = n (one input:
 // the reference's systems): the stack holds only [m0 | M] -- 1 / (n + 1) fewer bytes and matrix instructions -- and rad^u = sum |K g| is formed
 // from the n results of a generator group, which sit in the same lanes (one fused multiply-add per component and trajectory group).
-template <int R, int P, int NQ, bool SPLIT>
+template <int R, int P, int NQ>
 __global__ __launch_bounds__(256) void tz_genstack_mfma_kernel(GenstackMParams q) {
   constexpr int KS = (P + 3) / 4, GD = GsTile<R, P>::GD, GT = GsTile<R, P>::GT, LD = GsTile<R, P>::LD, MK = P - R;
   double kr[MK > 0 ? MK : 1][R];                 // K (uniform: scalar registers)
@@ -168,16 +168,14 @@ __global__ __launch_bounds__(256) void tz_genstack_mfma_kernel(GenstackMParams q
 #pragma unroll
     for (int c = 0; c < R; ++c) kr[jj][c] = q.K[jj * R + c];
   __shared__ double2 tile2[2][GT * GD / 2 + 2];                   // +2: the last A read of a tile may run 3 doubles past the group
-  __shared__ double xred[SPLIT ? 3 * P * NQ * 16 : 1];
   // (chunk, trajectory tile) of this block: the ntt tiles of a chunk are 8 blocks apart -> same XCD, consecutive waves of blocks
   const int bid = blockIdx.x;
   const int cgrp = bid / (8 * q.ntt), rem = bid % (8 * q.ntt);
-  const int chunk = cgrp * 8 + (rem & 7);
-  const int tt = SPLIT ? 0 : rem >> 3, sub = SPLIT ? rem >> 3 : 0;      // SPLIT: q.ntt counts the sub-blocks of a chunk (q.nsub)
+  const int chunk = cgrp * 8 + (rem & 7), tt = rem >> 3;
   if (chunk >= q.nchunk) return;
   const GsChunkM ch = q.chunks[chunk];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int tb = SPLIT ? tt * 16 * NQ : tt * 256 + wave * 64;     // first trajectory of this wave
+  const int tb = tt * 256 + wave * 64;                            // first trajectory of this wave
   // B operands: lane (k = lane >> 4, trajectory lane & 15 of group qq) holds Xi[4 s + k] of its trajectory
   double bx[KS][NQ];
   {
@@ -197,15 +195,9 @@ __global__ __launch_bounds__(256) void tz_genstack_mfma_kernel(GenstackMParams q
 #pragma unroll
     for (int qq = 0; qq < NQ; ++qq) acc[c][qq] = 0.0;
   const double2* src2 = reinterpret_cast<const double2*>(q.recs + (size_t)ch.q0 * GD);
-  // sub-range of the chunk's tiles this block walks (SPLIT only: nsub blocks share a chunk so that there are enough blocks to
-  // balance the chip; their partial sums are separate rows of `partial`, added by the reduce kernel in order)
-  const int ntile_all = (ch.nq + GT - 1) / GT;
-  const int t_lo = SPLIT ? (int)(((long long)ntile_all * sub) / q.nsub) : 0;
-  const int t_hi = SPLIT ? (int)(((long long)ntile_all * (sub + 1)) / q.nsub) : ntile_all;
-  const int ntile = t_hi - t_lo;
+  const int ntile = (ch.nq + GT - 1) / GT;
   double2 stA[LD], stB[LD];                                      // two tiles in flight: HBM latency is longer than one tile's products
-  auto fetch = [&](double2 (&stage)[LD], int tl) {               // global -> registers (tile t_lo + tl), nothing waits for it here
-    const int tg = t_lo + tl;
+  auto fetch = [&](double2 (&stage)[LD], int tg) {               // global -> registers (tile tg), nothing waits for it here
     const int nd2 = min(GT, ch.nq - tg * GT) * (GD / 2);
     const double2* s = src2 + (size_t)tg * (GT * GD / 2);
 #pragma unroll
@@ -219,8 +211,8 @@ __global__ __launch_bounds__(256) void tz_genstack_mfma_kernel(GenstackMParams q
   const int ci = 4 * R * P + (lane >> 4);                        // C (D layout): generator i = lane >> 4
   auto products = [&](int tl) {
     const double* buf = reinterpret_cast<const double*>(tile2[tl & 1]);
-    const int ng = min(GT, ch.nq - (t_lo + tl) * GT);
-    for (int g = SPLIT ? wave : 0; g < ng; g += SPLIT ? 4 : 1) {
+    const int ng = min(GT, ch.nq - tl * GT);
+    for (int g = 0; g < ng; ++g) {
       const double* gb = buf + g * GD;
       double ku[MK > 0 ? MK : 1][NQ];
 #pragma unroll
@@ -281,33 +273,13 @@ __global__ __launch_bounds__(256) void tz_genstack_mfma_kernel(GenstackMParams q
       v += __shfl_xor(v, 32);
       acc[c][qq] = v;
     }
-  if (SPLIT) {
-    if (wave > 0 && lane < 16) {
-#pragma unroll
-      for (int c = 0; c < P; ++c)
-#pragma unroll
-        for (int qq = 0; qq < NQ; ++qq) xred[(((wave - 1) * P + c) * NQ + qq) * 16 + lane] = acc[c][qq];
-    }
-    __syncthreads();
-    if (wave == 0 && lane < 16) {
-#pragma unroll
-      for (int qq = 0; qq < NQ; ++qq) {
-        const int b = tb + 16 * qq + lane;
-#pragma unroll
-        for (int c = 0; c < P; ++c) {
-          double v = acc[c][qq];
-          for (int w = 0; w < 3; ++w) v += xred[((w * P + c) * NQ + qq) * 16 + lane];
-          if (b < q.B) q.partial[((size_t)(chunk * q.nsub + sub) * q.B + b) * P + c] = v;
-        }
-      }
-    }
-  } else if (lane < 16) {
+  if (lane < 16) {
 #pragma unroll
     for (int qq = 0; qq < NQ; ++qq) {
       const int b = tb + 16 * qq + lane;
       if (b < q.B) {
 #pragma unroll
-        for (int c = 0; c < P; ++c) q.partial[((size_t)(chunk * q.nsub + sub) * q.B + b) * P + c] = acc[c][qq];
+        for (int c = 0; c < P; ++c) q.partial[((size_t)(chunk * q.nsub) * q.B + b) * P + c] = acc[c][qq];
       }
     }
   }
@@ -316,8 +288,8 @@ __global__ __launch_bounds__(256) void tz_genstack_mfma_kernel(GenstackMParams q
 // Few trajectories (<= 64), wave-private pipeline: every wave streams ITS tiles (GW = GT / 4 groups each, dealt round-robin to the
 // four waves) through its own double buffer in LDS -- global -> registers -> LDS -> A operands -- with wave-level ordering only: no
 // workgroup barrier inside the stream, so one wave's loads, another's LDS writes and a third's matrix instructions overlap instead
-// of meeting at a barrier per tile (the SPLIT form of tz_genstack_mfma_kernel: MFMA pipe 44 % busy, HBM at half its achievable rate,
-// neither saturated).  Same arithmetic per wave as there; the four waves' sums meet in LDS in wave order at the end.
+// of meeting at a barrier per tile (measured with one: MFMA pipe 44 % busy, HBM at half its achievable rate, neither saturated).  Same
+// arithmetic per wave as tz_genstack_mfma_kernel; the four waves' sums meet in LDS in wave order at the end.
 template <int R, int P, int NQ>
 __global__ __launch_bounds__(256) void tz_genstack_mfma_narrow_kernel(GenstackMParams q) {
   constexpr int KS = (P + 3) / 4, GD = GsTile<R, P>::GD, GW = (GsTile<R, P>::GT >= TZ_GS_GWDIV) ? GsTile<R, P>::GT / TZ_GS_GWDIV : 1, MK = P - R;

@@ -12,9 +12,7 @@
 
 #define TZ_MINWAVES 4
 #define TZ_RLEV_CARRY_MAX 2      // diagonal-shift level (1e-6) a warm-started step may inherit from the step before ...
-#ifndef TZ_RLEV_GATE
 #define TZ_RLEV_GATE 1e6         // ... from the iteration on whose complementarity is within this factor of the one at which that step broke down
-#endif
 #define TZ_SEED_VIOL_MAX 0.1     // stored start: largest violation of the new rows (equilibrated) it is still used at
 // H lives in LDS as tile rows of quads (4 column tiles); a quad is 4 matrix rows of 16 doubles padded to TZ_QROW = 17 so
 // that neither the MFMA accumulator access (row-major inside the quad) nor the column access of the factorisation and the
@@ -111,14 +109,13 @@ struct IpmParams {
   // problems with more than 64 variables (tz_tt.hip.h): H in the tile-triangle layout, TS doubles per tile, blocked Gram plan
   int TS, ntile, gu;       // gu: tiles per side of a unit of the blocked Gram
   const struct TzGUnit* gunits; const int* gunit_ptr;      // units of the blocked Gram, grouped per wave (TZ_NWAVES + 1 offsets)
-  int chol1;                  // Tz <= 16: one wave factors H while the other three form the predictor's right-hand side
   int ksplit;                 // Gram by tz_form_H_ksplit (Tz <= TZ_KS_TZ) instead of the item plan
   int warm; double warm_floor;   // warm != 0: start from the x / lambda already stored for the trajectory (closed-loop steps)
   double warm_gain, warm_cap;    // warm point pushed into the cone by sigma = min(max(warm_floor, warm_gain * violation of the new rows), warm_cap)
   double aff_thr, aff_mu;        // predictor step taken as the step (no corrector solve) when it reaches aff_thr of the way to the
                                  // boundary un-damped and leaves mu_aff <= aff_mu * mu; aff_thr > 1 disables
   unsigned long long* work;   // [0] += factorisations, [1] += trajectory solves, [2] = max over trajectories of the factorisations of one launch; may be null
-  unsigned long long* prof;   // TZ_PROF=1: per-phase cycle sums of workgroup 0 (diagnostic; no output depends on it)
+  unsigned long long* prof;   // diagnostic build: per-phase cycle sums of workgroup 0 (no output depends on it)
   FuseParams F;               // F.on != 0: whole closed-loop step in this launch (q, h, prestatus above are then unused)
 };
 
@@ -597,8 +594,7 @@ __device__ inline double tz_quad_bcast(double v) {                     // value 
 // Factor the diagonal tile (pp, pp) (every calling thread redundantly, from LDS) and solve the panel rows of tiles (I, pp),
 // I > pp, with the calling threads tid = 0 .. nthr-1.  Thread tid == 0 stores dinv[pp] = inverse of the diagonal factor.
 // The diagonal tile itself is not written back: nothing reads it again.
-__device__ inline void tz_factor_col(int Tz, double* Hq, double* dinv, int* flag, int pp, int tid, int nthr, unsigned long long* pacc = nullptr) {
-  unsigned long long tq0 = pacc ? __builtin_amdgcn_s_memtime() : 0;
+__device__ inline void tz_factor_col(int Tz, double* Hq, double* dinv, int* flag, int pp, int tid, int nthr) {
   const int dbase = (tz_qprefix(pp) + (pp >> 2)) * TZ_QSTR + 4 * (pp & 3);
   const double a00 = Hq[dbase], a10 = Hq[dbase + TZ_QROW], a11 = Hq[dbase + TZ_QROW + 1];
   const double a20 = Hq[dbase + 2 * TZ_QROW], a21 = Hq[dbase + 2 * TZ_QROW + 1], a22 = Hq[dbase + 2 * TZ_QROW + 2];
@@ -633,7 +629,6 @@ __device__ inline void tz_factor_col(int Tz, double* Hq, double* dinv, int* flag
       m[12] = m30; m[13] = m31; m[14] = m32; m[15] = i33;
     }
   }
-  if (pacc) { unsigned long long tq1 = __builtin_amdgcn_s_memtime(); pacc[PH_CH_DIAG] += tq1 - tq0; tq0 = tq1; }
   for (int t = tid; t < 4 * (Tz - pp - 1); t += nthr) {      // x L_pp' = a
     const int I = pp + 1 + (t >> 2), i = t & 3;
     const int base = (tz_qprefix(I) + (pp >> 2)) * TZ_QSTR + TZ_QROW * i + 4 * (pp & 3);
@@ -644,64 +639,8 @@ __device__ inline void tz_factor_col(int Tz, double* Hq, double* dinv, int* flag
     const double x3 = (b3 - x0 * l30 - x1 * l31 - x2 * l32) * i33;
     Hq[base] = x0; Hq[base + 1] = x1; Hq[base + 2] = x2; Hq[base + 3] = x3;
   }
-  if (pacc) pacc[PH_CH_PANEL] += __builtin_amdgcn_s_memtime() - tq0;
 }
 
-// In-place tile-4 LEFT-looking Cholesky.  For tile column pp the tiles (I, pp), I >= pp, are brought up to date with all
-// finished columns k < pp in registers (four tile rows per MFMA = the four blocks; two LDS reads per MFMA and no
-// read-modify-write of H), written once, then the diagonal tile is factored and the panel solved by all threads.
-// Groups of four tile rows are dealt round-robin to the four waves.  Two workgroup barriers per column.
-__device__ inline bool tz_cholesky(const IpmParams& p, double* Hq, double* dinv, int* flag, unsigned long long* pacc = nullptr) {
-  const int Tz = p.Tz;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int k = lane >> 4, blk = (lane >> 2) & 3, ij = lane & 3;       // operand layout (k', blk, i|j); D layout (i = k, blk, j = ij)
-  for (int pp = 0; pp < Tz; ++pp) {
-    unsigned long long tc0 = pacc ? __builtin_amdgcn_s_memtime() : 0;
-    if (pp > 0) {
-      const int pq = pp >> 2, po = 4 * (pp & 3);
-      const double* pb = Hq + tz_qprefix(pp) * TZ_QSTR + TZ_QROW * ij + k;         // L(4pp + j, 4k2 + k'), j = ij : + off(k2)
-      for (int g = wave; pp + 4 * g < Tz; g += 2 * TZ_NWAVES) {            // two row groups at a time: four independent MFMA chains
-        const int Ia = pp + 4 * g + blk, Ib = Ia + 4 * TZ_NWAVES;
-        const bool va = Ia < Tz, vb = Ib < Tz;
-        const int qa = tz_qprefix(va ? Ia : pp), qb = tz_qprefix(vb ? Ib : pp);
-        const double* pa = Hq + qa * TZ_QSTR + TZ_QROW * ij + k;             // L(4Ia + i, 4k2 + k'), i = ij : + off(k2)
-        const double* pa2 = Hq + qb * TZ_QSTR + TZ_QROW * ij + k;
-        double* pc = Hq + (qa + pq) * TZ_QSTR + TZ_QROW * k + po + ij;       // H(4Ia + i', 4pp + j'), i' = k, j' = ij
-        double* pc2 = Hq + (qb + pq) * TZ_QSTR + TZ_QROW * k + po + ij;
-        double a0 = *pc, a1 = 0.0, c0 = vb ? *pc2 : 0.0, c1 = 0.0;
-        int off = 0, k2 = 0;
-        for (; k2 + 1 < pp; k2 += 2) {
-          const int off1 = off + 4 + (((k2 & 3) == 3) ? TZ_QSTR - 16 : 0);
-          const double nb0 = -pb[off], nb1 = -pb[off1];
-          const double x0 = pa[off], x1 = pa[off1], y0 = pa2[off], y1 = pa2[off1];
-          a0 = __builtin_amdgcn_mfma_f64_4x4x4f64(x0, nb0, a0, 0, 0, 0);
-          c0 = __builtin_amdgcn_mfma_f64_4x4x4f64(y0, nb0, c0, 0, 0, 0);
-          a1 = __builtin_amdgcn_mfma_f64_4x4x4f64(x1, nb1, a1, 0, 0, 0);
-          c1 = __builtin_amdgcn_mfma_f64_4x4x4f64(y1, nb1, c1, 0, 0, 0);
-          off = off1 + 4 + ((((k2 + 1) & 3) == 3) ? TZ_QSTR - 16 : 0);
-        }
-        if (k2 < pp) {
-          const double nb0 = -pb[off];
-          a0 = __builtin_amdgcn_mfma_f64_4x4x4f64(pa[off], nb0, a0, 0, 0, 0);
-          c0 = __builtin_amdgcn_mfma_f64_4x4x4f64(pa2[off], nb0, c0, 0, 0, 0);
-        }
-        if (va) *pc = a0 + a1;
-        if (vb) *pc2 = c0 + c1;
-      }
-      if (pacc) { unsigned long long t1 = __builtin_amdgcn_s_memtime(); pacc[PH_CH_UPD] += t1 - tc0; tc0 = t1; }
-      __syncthreads();
-      if (pacc) { unsigned long long t1 = __builtin_amdgcn_s_memtime(); pacc[PH_CH_BAR] += t1 - tc0; tc0 = t1; }
-    }
-    tz_factor_col(Tz, Hq, dinv, flag, pp, threadIdx.x, TZ_THREADS, pacc);
-    if (pacc) tc0 = __builtin_amdgcn_s_memtime();
-    __syncthreads();
-    if (pacc) pacc[PH_CH_BAR] += __builtin_amdgcn_s_memtime() - tc0;
-  }
-  return *flag == 0;
-}
-
-// The same factorisation by ONE wave (wave-level ordering of its own LDS traffic instead of workgroup barriers), for matrices
-// of at most 16 tile columns: the other three waves are free to run an independent G' product meanwhile (tz_ipm_kernel).
 __device__ inline void tz_wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
@@ -718,6 +657,11 @@ __device__ inline bool tz_spin_until(const int* f, int target) {
   return false;
 }
 
+// In-place tile-4 LEFT-looking Cholesky by ONE wave, for matrices of at most 16 tile columns (nz <= 64).  For tile column pp the
+// tiles (I, pp), I >= pp, are brought up to date with all finished columns k < pp in registers (four tile rows per MFMA = the four
+// blocks; two LDS reads per MFMA and no read-modify-write of H), written once, then the diagonal tile is factored and the panel
+// solved.  Wave-level ordering of its own LDS traffic instead of workgroup barriers: the other three waves are free to run an
+// independent G' product meanwhile (tz_ipm_kernel).
 // prog (LDS, may be null): number of finished tile columns, published after each one -- column pp of L and inv(L_pp,pp) are final
 // then, which is all the forward substitution trailing on another wave (tz_fwd_trailing) needs for its step pp.
 __device__ inline void tz_cholesky_wave(const IpmParams& p, double* Hq, double* dinv, int* flag, int* prog = nullptr) {
@@ -762,88 +706,6 @@ __device__ inline void tz_cholesky_wave(const IpmParams& p, double* Hq, double* 
     tz_wave_sync();
     if (prog && lane == 0) __hip_atomic_store(prog, pp + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
   }
-}
-
-// Solve (L L') out = rhs.  Thread t owns row t (nzp <= 256) in a register; wave w owns the 64-row block w.
-// Forward: the blocks are finished one after the other.  Inside a block the 16 tile steps run wave-synchronously (owner
-// quad finishes its 4 unknowns with DPP broadcasts and publishes them in LDS, the other lanes of the SAME wave pick them up:
-// in-wave LDS ordering, no workgroup barrier); between blocks one barrier and one bulk update of the rows of later blocks.
-// Backward: the mirror image.  ybuf: nzp doubles of LDS.
-__device__ inline void tz_chol_solve(const IpmParams& p, const double* Hq, const double* dinv,
-                                     const double* rhs, double* ybuf, double* out) {
-  const int Tz = p.Tz, nzp = p.nzp;
-  const int t = tz_tid(), jq = t & 3, tq = t >> 2, wave = t >> 6;
-  const int nblk = (Tz + 15) >> 4;
-  double rv = (t < nzp) ? rhs[t] : 0.0;
-  const int rowbase = tz_qprefix(tq) * TZ_QSTR + TZ_QROW * jq;                    // + (I>>2)*64 + 4(I&3): L(t, 4I + .)
-  for (int blkI = 0; blkI < nblk; ++blkI) {                             // ---- forward: L y = rhs
-    const int I0 = 16 * blkI, I1 = min(Tz, I0 + 16);
-    if (wave == blkI) {
-      for (int I = I0; I < I1; ++I) {
-        if (tq == I) {
-          const double a0 = tz_quad_bcast<0>(rv), a1 = tz_quad_bcast<1>(rv), a2 = tz_quad_bcast<2>(rv), a3 = tz_quad_bcast<3>(rv);
-          const double* m = dinv + I * 16 + 4 * jq;                      // row jq of M (lower)
-          rv = m[0] * a0 + m[1] * a1 + m[2] * a2 + m[3] * a3;
-          ybuf[t] = rv;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        if (tq > I && t < nzp) {
-          const int base = rowbase + (I >> 2) * TZ_QSTR + 4 * (I & 3);
-          const double* y = ybuf + 4 * I;
-          rv -= Hq[base] * y[0] + Hq[base + 1] * y[1] + Hq[base + 2] * y[2] + Hq[base + 3] * y[3];
-        }
-      }
-    }
-    if (blkI + 1 < nblk) {
-      __syncthreads();
-      if (wave > blkI && t < nzp) {                                      // bulk: rows of later blocks take this block's y
-        double acc = 0.0;
-        for (int I = I0; I < I1; ++I) {
-          const int base = rowbase + (I >> 2) * TZ_QSTR + 4 * (I & 3);
-          const double* y = ybuf + 4 * I;
-          acc += Hq[base] * y[0] + Hq[base + 1] * y[1] + Hq[base + 2] * y[2] + Hq[base + 3] * y[3];
-        }
-        rv -= acc;
-      }
-    }
-  }
-  const int colbase = (t >> 4) * TZ_QSTR + 4 * ((t >> 2) & 3) + (t & 3);     // + qprefix(I)*64 + 16k: L(4I + k, t)
-  for (int blkI = nblk - 1; blkI >= 0; --blkI) {                        // ---- backward: L' x = y
-    const int I0 = 16 * blkI, I1 = min(Tz, I0 + 16);
-    if (wave == blkI) {
-      for (int I = I1 - 1; I >= I0; --I) {
-        if (tq == I) {
-          const double y0 = tz_quad_bcast<0>(rv), y1 = tz_quad_bcast<1>(rv), y2 = tz_quad_bcast<2>(rv), y3 = tz_quad_bcast<3>(rv);
-          const double* m = dinv + I * 16 + jq;                          // column jq of M
-          rv = m[0] * y0 + m[4] * y1 + m[8] * y2 + m[12] * y3;
-          ybuf[t] = rv;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        if (tq < I && tq >= I0) {
-          const int base = tz_qprefix(I) * TZ_QSTR + colbase;
-          const double* x = ybuf + 4 * I;
-          rv -= Hq[base] * x[0] + Hq[base + TZ_QROW] * x[1] + Hq[base + 2 * TZ_QROW] * x[2] + Hq[base + 3 * TZ_QROW] * x[3];
-        }
-      }
-    }
-    if (blkI > 0) {
-      __syncthreads();
-      if (wave < blkI) {                                                 // bulk: rows of earlier blocks take this block's x
-        double acc = 0.0;
-        for (int I = I0; I < I1; ++I) {
-          const int base = tz_qprefix(I) * TZ_QSTR + colbase;
-          const double* x = ybuf + 4 * I;
-          acc += Hq[base] * x[0] + Hq[base + TZ_QROW] * x[1] + Hq[base + 2 * TZ_QROW] * x[2] + Hq[base + 3 * TZ_QROW] * x[3];
-        }
-        rv -= acc;
-      }
-    }
-  }
-  if (t < nzp) out[t] = rv;
 }
 
 // (L L') out = rhs for matrices of at most 16 tile columns (nzp <= 64): wave 0 alone, lane = row, the value of every unknown
@@ -1255,9 +1117,9 @@ retry_solve:
     __syncthreads();
     if constexpr (TT) { okf = tz_cholesky_tt(p, Hq, dinv, dfac, flag); TZ_TT_AFTER_CHOL(p, Hq, dinv); TZ_TT_SOLVE(p, Hq, dinv, r1v, tmpz, xv); }
     else {
-    if (p.chol1) { if (wave0) tz_cholesky_wave(p, Hq, dinv, flag); __syncthreads(); okf = (*flag == 0); }
-    else okf = tz_cholesky(p, Hq, dinv, flag);
-    if (p.chol1) tz_chol_solve_wave(p, Hq, dinv, r1v, xv); else tz_chol_solve(p, Hq, dinv, r1v, tmpz, xv);
+    if (wave0) tz_cholesky_wave(p, Hq, dinv, flag);
+    __syncthreads(); okf = (*flag == 0);
+    tz_chol_solve_wave(p, Hq, dinv, r1v, xv);
     }
     tz_ell_gemv<MAXR, TT>(p, xv, pl, rseg_, gx_);
     if (PARK) { TZ_ROWS(k, r) gL[r] = gx_[k]; }
@@ -1332,7 +1194,6 @@ retry_solve:
         rlev = rlev_carry < TZ_RLEV_CARRY_MAX ? rlev_carry : TZ_RLEV_CARRY_MAX;
     }
     bool okc;
-    bool have_y = false;                                // tmpz holds y = inv(L) r1 (forward substitution done while factoring)
     // A factorisation that breaks down (degenerate problems late in the solve: the weights of active and inactive rows are 1e18
     // apart and H loses definiteness in rounding) raises the diagonal-shift level -- 1 .. 4 = 1e-9, 1e-6, 1e-3, 1, kept for the
     // rest of the solve -- and the iteration is repeated from the same point (it counts as an iteration).  A shifted H only damps
@@ -1351,11 +1212,11 @@ retry_solve:
       }
     }
     // ---- predictor (rc = s*lam):  H dx = -(P x + q) - G'(w rp).  The factorisation of H and the two products on the right
-    // are independent: with chol1 wave 0 factors while waves 1-3 form the right-hand side.
+    // are independent: with at most 64 variables wave 0 factors while waves 1-3 form the right-hand side.
     TZ_ROWS(k, r) vin[r] = w_[k] * rp_[k];
     if (t == 0) { flag[2] = 0; flag[3] = 0; }        // columns factored / waves done with the right-hand side
     __syncthreads();
-    if (!TT && p.chol1) {
+    if constexpr (!TT) {
       if (wave0) {
         __builtin_amdgcn_s_setprio(TZ_PRIO);                 // the serial stretch of this workgroup: ahead of the co-resident waves
         tz_cholesky_wave(p, Hq, dinv, flag, flag + 2);
@@ -1382,7 +1243,6 @@ retry_solve:
       }
       __syncthreads();
       okc = (*flag == 0);
-      have_y = true;
       TZ_STAMP(PH_CHOL);
     } else {
       if (wave0) tz_gemvT_partial<NCG, 0, 1>(p.P, p.nP, nzp, xv, part2);
@@ -1395,8 +1255,8 @@ retry_solve:
       }
       __syncthreads();
       TZ_STAMP(PH_GEMVT);
-      if constexpr (TT) { okc = tz_cholesky_tt(p, Hq, dinv, dfac, flag, (PROF && t == 0) ? acc_ph : nullptr); TZ_TT_AFTER_CHOL(p, Hq, dinv); }
-      else okc = tz_cholesky(p, Hq, dinv, flag, (PROF && t == 0) ? acc_ph : nullptr);
+      okc = tz_cholesky_tt(p, Hq, dinv, dfac, flag, (PROF && t == 0) ? acc_ph : nullptr);
+      TZ_TT_AFTER_CHOL(p, Hq, dinv);
       TZ_STAMP(PH_CHOL);
     }
     if (!okc) {
@@ -1410,7 +1270,7 @@ retry_solve:
     }
     TZ_FRESH_T();
     if constexpr (TT) TZ_TT_SOLVE(p, Hq, dinv, r1v, tmpz, dxv);
-    else if (p.chol1) tz_chol_solve_wave(p, Hq, dinv, have_y ? tmpz : r1v, dxv, have_y); else tz_chol_solve(p, Hq, dinv, r1v, tmpz, dxv);
+    else tz_chol_solve_wave(p, Hq, dinv, tmpz, dxv, true);            // tmpz: y = inv(L) r1, left there by tz_fwd_trailing
     __syncthreads();
     TZ_STAMP(PH_SOLVE);
     tz_ell_gemv<MAXR, TT>(p, dxv, pl, rseg_, g_);
@@ -1466,7 +1326,7 @@ retry_solve:
     __syncthreads();
     TZ_STAMP(PH_GEMVT);
     if constexpr (TT) TZ_TT_SOLVE(p, Hq, dinv, r1v, tmpz, dxv);
-    else if (p.chol1) tz_chol_solve_wave(p, Hq, dinv, r1v, dxv); else tz_chol_solve(p, Hq, dinv, r1v, tmpz, dxv);
+    else tz_chol_solve_wave(p, Hq, dinv, r1v, dxv);
     __syncthreads();
     TZ_STAMP(PH_SOLVE);
     tz_ell_gemv<MAXR, TT>(p, dxv, pl, rseg_, g_);

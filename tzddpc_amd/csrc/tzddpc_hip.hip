@@ -4,17 +4,8 @@
 // numeric result comes out of a kernel.
 #include "tz_kernels.hip.h"
 
-// Experiment switches (tools/*.sh, tools/*.py) are read from the environment by the DIAGNOSTIC build only (libtzddpc_hip_prof.so,
-// -DTZ_PROFILE=1); the release library reads no environment variable: what a caller may choose goes through tz_problem_desc
-// (plan_flags) and the tz_problem_set_* entry points.
-static inline const char* tz_dev_getenv(const char* name) {
-#if TZ_PROFILE
-  return getenv(name);
-#else
-  (void)name;
-  return nullptr;
-#endif
-}
+// Neither build of the library reads an environment variable: what a caller may choose goes through tz_problem_desc (plan_flags)
+// and the tz_problem_set_* entry points.  The diagnostic build (libtzddpc_hip_prof.so, -DTZ_PROFILE=1) only adds per-phase clocks.
 #include "../../include/tzddpc.h"
 
 #include <algorithm>
@@ -194,12 +185,11 @@ struct tz_problem {
   double t_ms[K_COUNT] = {0, 0, 0, 0};
   int64_t t_count[K_COUNT] = {0, 0, 0, 0};
   int lastB = 0;
-  bool prof = false;
+  bool prof = TZ_PROFILE;      // diagnostic build: per-phase clocks of workgroup 0 (tz_debug_fetch item 6)
   bool have_prev = false; int prevB = 0;   // x / s / lambda of the previous closed-loop step are valid for prevB trajectories
   DevBuf<double> ref_x, ref_lam;          // stored start (tz_problem_store_start): solution and multipliers of one reference solve
   bool have_ref = false;
-  double warm_floor = 1e-8, warm_gain = 1.0, warm_cap = 1e300, mu_factor = 1e-3, res_factor = 100.0, aff_thr = 0.99, aff_mu = 1e-3;
-  bool warm_enabled = true;
+  double warm_floor = 1e-8, warm_gain = 1.0, warm_cap = 1e300, mu_factor = 1e-3, res_factor = 100.0;
   int ntube = 0;
   bool tt = false;             // tile-triangle layout / blocked Gram / two-phase Cholesky (nz > 64 or more than 1024 rows)
   int TS = 16, ntile = 0, gu = 0;
@@ -207,11 +197,9 @@ struct tz_problem {
   DevBuf<TzGUnit> gunits; DevBuf<int> gunit_ptr;
   DevBuf<int> vpos;            // staircase ordering (tile-triangle class): device position of v[k, j]; null = identity
   std::vector<int> permc, permr;   // device variable / row i is the caller's permc[i] / permr[i] (empty = identity)
-  bool chol1 = false;          // single-wave Cholesky overlapped with the predictor's G' product (Tz <= 16; TZ_CHOL1=0 disables)
-  bool ksplit = false;         // Gram by k-split (Tz <= TZ_KS_TZ; TZ_KSPLIT=0 keeps the item plan)
+  bool ksplit = false;         // Gram by k-split (Tz <= TZ_KS_TZ; TZ_PLAN_ITEM_GRAM keeps the item plan)
   bool fuse_enabled = true;    // closed-loop steps in one launch (TZ_PLAN_UNFUSED: four kernels per step, same arithmetic)
   bool staircase = false;      // tile-triangle class: variables in time order, rows by last non-zero column (library-internal)
-  bool toeplitz = false;       // G x / G'v as block-Toeplitz convolutions over the horizon (not built: see DESIGN.md)
   bool lean_epilogue = false;  // FuseParams::lean_epilogue
   struct tz_genstack* tube_stack = nullptr;   // literal problems: decision-independent generators, evaluated per solve (not owned)
   DevBuf<double> ts_zeta, ts_c, ts_rx, ts_ru;  int ts_cap = 0;
@@ -300,12 +288,12 @@ IpmParams ipm_params(tz_problem* p, int B, int* d_status, int* d_iters, bool war
   ip.prof = p->prof ? p->prof_buf.p : nullptr;
   ip.work = p->timing ? p->work_buf.p : nullptr;
   ip.TS = p->TS; ip.ntile = p->ntile; ip.gu = p->gu; ip.gunits = p->gunits.p; ip.gunit_ptr = p->gunit_ptr.p;
-  ip.nklist = p->nklist; ip.nP = p->nP; ip.ksplit = p->ksplit ? 1 : 0; ip.chol1 = p->chol1 ? 1 : 0; ip.ntube = p->ntube;
+  ip.nklist = p->nklist; ip.nP = p->nP; ip.ksplit = p->ksplit ? 1 : 0; ip.ntube = p->ntube;
   ip.shift_policy = p->have_shift ? p->shift_policy : 0; ip.shift_quiet = p->shift_quiet;
   ip.shift_state = p->shift_state.p;
   ip.sx = p->shift_var.p; ip.sr = p->shift_row.p; ip.sxs = p->shift_xs.p; ip.sls = p->shift_ls.p;
   ip.warm = warm ? 1 : 0; ip.warm_floor = p->warm_floor;
-  ip.warm_gain = p->warm_gain; ip.warm_cap = p->warm_cap; ip.aff_thr = p->aff_thr; ip.aff_mu = p->aff_mu;
+  ip.warm_gain = p->warm_gain; ip.warm_cap = p->warm_cap; ip.aff_thr = 0.99; ip.aff_mu = 1e-3;
   ip.prev_status = warm ? p->prev_status.p : nullptr;
   ip.status_copy = track_prev ? p->prev_status.p : nullptr;
   ip.F.on = 0;
@@ -324,7 +312,7 @@ int launch_step_fused(tz_problem* p, int B, double* d_x, double* d_xbar, double*
   IpmParams ip = ipm_params(p, B, d_status, p->iters.p, warm, true);
   FuseParams& F = ip.F;
   F.on = 1; F.npar = p->npar; F.ntheta = p->ntheta; F.lean_epilogue = p->lean_epilogue ? 1 : 0; F.sticky_fresh = sticky_fresh ? 1 : 0;
-  F.nsteps = nsteps; F.warm_steps = p->warm_enabled ? 1 : 0; ip.warm_steps = F.warm_steps;
+  F.nsteps = nsteps; F.warm_steps = 1; ip.warm_steps = F.warm_steps;
   F.w_step = ss.w; F.u_step = ss.u; F.x_step = ss.x; F.cost_step = ss.cost;
   F.tube = TubeParams{B, p->n, p->m, p->N, p->pmax, p->ntheta, p->CKpow.p, p->Ttube.p, p->power.p, d_xbar, d_e, nullptr, nullptr};
   F.qmap = p->q.view(); F.hmap = p->h.view(); F.parmap = p->par.view(); F.par_lo = p->par_lo.p; F.par_hi = p->par_hi.p;
@@ -527,11 +515,11 @@ int tz_genstack_create(int device, const tz_genstack_desc* d, tz_genstack** out)
   g->nchunk = (int)chunks.size();
   // matrix-core layout of the sorted stack (dimensions with a compiled instance): per group of 4 generators (a chunk is padded
   // with zero generators) [component c < P][generator i < 4][inner k < P] of Mext = [M; K M], then [c][i] of m0ext = [m0; K m0]
-  g->mfma = (p >= 3 && p <= 7) && !tz_dev_getenv("TZ_GS_VALU");
+  g->mfma = (p >= 3 && p <= 7);
   // one input (the reference's systems): a second copy of the stack holds only the n rows [m0 | M] -- 1 / (n + 1) fewer bytes and matrix
   // instructions -- and K g is formed in the kernel; it serves every batch except 33 .. 64 trajectories, where the extra vector
-  // arithmetic of the narrow kernel costs more than the rows save (measured: tools/k1g_ab.sh).  TZ_GS_KROWS=1: appended rows only.
-  g->rows_mf = (m == 1 && !tz_dev_getenv("TZ_GS_KROWS")) ? n : p;
+  // arithmetic of the narrow kernel costs more than the rows save (measured: LAB_NOTEBOOK.md, "K g formed in the kernel").
+  g->rows_mf = (m == 1) ? n : p;
   if (g->mfma && !chunks.empty()) {
     std::vector<GsChunkM> cm;
     std::vector<double> ext((size_t)p * (p + 1));
@@ -630,24 +618,16 @@ static int gs_eval(tz_genstack* g, int B, const double* de0, const double* dz, d
     // many: 256 per workgroup, the stack is re-read from L2 by the tiles of a chunk, which share an XCD
     const bool split = B <= 64;
     const int nq = B <= 16 ? 1 : (B <= 32 ? 2 : 4);
-    nsub = split ? 2 : 1;                             // two blocks per chunk when every block streams its tiles once (measured at 32 trajectories,
-    if (split) {                                      // 636 chunks: 1 -> 0.0670 ms, 2 -> 0.0641 ms, 4 -> 0.120 ms: the un-overlapped prologue of short blocks)
-      const char* e = tz_dev_getenv("TZ_GS_NSUB");
-      if (e) nsub = std::min(TZ_GS_MAXSUB, std::max(1, atoi(e)));
-    }
+    nsub = split ? TZ_GS_NARROW_SUB : 1;
     const int ntt = split ? nsub : (B + 255) / 256;
     const bool krows = g->rows_mf == p || (B > 32 && B <= 64);       // which copy of the stack: K rows appended, or formed in the kernel
     GenstackMParams qm{B, n, m, g->N, g->nchunk, ntt, nsub, krows ? g->recs_mf.p : g->recs_mfn.p, g->K.p, g->chunks_m.p, de0, dz, g->partial.p};
     const dim3 gm((unsigned)(((g->nchunk + 7) / 8) * 8 * ntt));
-    const bool narrow = split && !tz_dev_getenv("TZ_GS_NO_NARROW");     // wave-private pipeline (no barrier in the stream); the switch keeps the barrier form
 #define TZ_GS_LAUNCH(RR, PP) do { \
-      if (!split) hipLaunchKernelGGL((tz_genstack_mfma_kernel<RR, PP, 4, false>), gm, dim3(256), 0, st, qm); \
-      else if (narrow && nq == 1) hipLaunchKernelGGL((tz_genstack_mfma_narrow_kernel<RR, PP, 1>), gm, dim3(256), 0, st, qm); \
-      else if (narrow && nq == 2) hipLaunchKernelGGL((tz_genstack_mfma_narrow_kernel<RR, PP, 2>), gm, dim3(256), 0, st, qm); \
-      else if (narrow) hipLaunchKernelGGL((tz_genstack_mfma_narrow_kernel<RR, PP, 4>), gm, dim3(256), 0, st, qm); \
-      else if (nq == 1) hipLaunchKernelGGL((tz_genstack_mfma_kernel<RR, PP, 1, true>), gm, dim3(256), 0, st, qm); \
-      else if (nq == 2) hipLaunchKernelGGL((tz_genstack_mfma_kernel<RR, PP, 2, true>), gm, dim3(256), 0, st, qm); \
-      else hipLaunchKernelGGL((tz_genstack_mfma_kernel<RR, PP, 4, true>), gm, dim3(256), 0, st, qm); } while (0)
+      if (!split) hipLaunchKernelGGL((tz_genstack_mfma_kernel<RR, PP, 4>), gm, dim3(256), 0, st, qm); \
+      else if (nq == 1) hipLaunchKernelGGL((tz_genstack_mfma_narrow_kernel<RR, PP, 1>), gm, dim3(256), 0, st, qm); \
+      else if (nq == 2) hipLaunchKernelGGL((tz_genstack_mfma_narrow_kernel<RR, PP, 2>), gm, dim3(256), 0, st, qm); \
+      else hipLaunchKernelGGL((tz_genstack_mfma_narrow_kernel<RR, PP, 4>), gm, dim3(256), 0, st, qm); } while (0)
     if (krows) {
       switch (p) {
         case 3: TZ_GS_LAUNCH(3, 3); break;
@@ -690,7 +670,7 @@ int tz_genstack_intervals(tz_genstack* g, int32_t B, const double* e0, const dou
   const double *de0 = nullptr, *dz = nullptr;
   int rc = gs_inputs(g, B, e0, zeta, mem, &de0, &dz);
   if (rc) return rc;
-  { const size_t need = (size_t)std::max(g->nchunk, 1) * (B <= 64 ? TZ_GS_MAXSUB : 1) * B * p; if (need > g->pcap) { TZ_HIP(g->partial.alloc(need)); g->pcap = need; } }
+  { const size_t need = (size_t)std::max(g->nchunk, 1) * (B <= 64 ? TZ_GS_NARROW_SUB : 1) * B * p; if (need > g->pcap) { TZ_HIP(g->partial.alloc(need)); g->pcap = need; } }
   double *dc = centre, *drx = rad_x, *dru = rad_u;
   if (mem == TZ_MEM_HOST) {
     TZ_HIP(g->o_c.alloc((size_t)B * g->nseg * n)); TZ_HIP(g->o_rx.alloc((size_t)B * g->nseg * n)); TZ_HIP(g->o_ru.alloc((size_t)B * g->nseg * m));
@@ -720,7 +700,7 @@ int tube_stack_theta(tz_problem* p, int B, const double* d_e0, hipStream_t st) {
     TZ_HIP(p->ts_c.alloc((size_t)B * g->nseg * n)); TZ_HIP(p->ts_rx.alloc((size_t)B * g->nseg * n)); TZ_HIP(p->ts_ru.alloc((size_t)B * g->nseg * m));
     p->ts_cap = B;
   }
-  { const size_t need = (size_t)std::max(g->nchunk, 1) * (B <= 64 ? TZ_GS_MAXSUB : 1) * B * pq; if (need > g->pcap) { TZ_HIP(g->partial.alloc(need)); g->pcap = need; } }
+  { const size_t need = (size_t)std::max(g->nchunk, 1) * (B <= 64 ? TZ_GS_NARROW_SUB : 1) * B * pq; if (need > g->pcap) { TZ_HIP(g->partial.alloc(need)); g->pcap = need; } }
   int rc = gs_eval(g, B, d_e0, p->ts_zeta.p, p->ts_c.p, p->ts_rx.p, p->ts_ru.p, st);
   if (rc) return rc;
   ThetaStackParams q{B, n, m, p->N, g->nseg, p->ntheta, p->ts_c.p, p->ts_rx.p, p->ts_ru.p, p->theta.p};
@@ -776,6 +756,8 @@ int tz_problem_create(int device, const tz_problem_desc* d, tz_problem** out) {
     if (d->power[k] < 0 || d->power[k] > d->pmax) TZ_FAIL(TZ_ERR_INVALID, "power[%d]=%d outside 0..pmax", k, d->power[k]);
   for (int r = 0; r < d->mi; ++r)
     if (d->row_of[r] < 0 || d->row_of[r] >= std::max(d->nc_rows, 1)) TZ_FAIL(TZ_ERR_INVALID, "row_of[%d] out of range", r);
+  const int32_t known_flags = TZ_PLAN_UNFUSED | TZ_PLAN_ITEM_GRAM | TZ_PLAN_NO_STAIRCASE;
+  if (d->plan_flags & ~known_flags) TZ_FAIL(TZ_ERR_INVALID, "plan_flags 0x%x: unknown bits 0x%x", (unsigned)d->plan_flags, (unsigned)(d->plan_flags & ~known_flags));
   int ndev = 0;
   TZ_HIP(hipGetDeviceCount(&ndev));
   if (ndev <= 0) TZ_FAIL(TZ_ERR_HIP, "no HIP device visible: the TZDDPC hot path has no CPU fallback");
@@ -809,7 +791,7 @@ int tz_problem_create(int device, const tz_problem_desc* d, tz_problem** out) {
   std::vector<int> permc((size_t)nz), permr((size_t)mi), invc((size_t)nz), invr((size_t)mi);
   std::iota(permc.begin(), permc.end(), 0); std::iota(permr.begin(), permr.end(), 0);
   const int nv = d->N * d->m;
-  if (p->tt && !(d->plan_flags & TZ_PLAN_NO_STAIRCASE) && tz_dev_getenv("TZ_NO_STAIRCASE") == nullptr) {
+  if (p->tt && !(d->plan_flags & TZ_PLAN_NO_STAIRCASE)) {
     std::vector<int> rowt((size_t)mi, -1), colt((size_t)nz, 1 << 30);
     for (int r = 0; r < mi; ++r) for (int c = 0; c < nv; ++c) if (d->G[(size_t)r * nz + c] != 0.0) rowt[r] = std::max(rowt[r], c / d->m);
     for (int c = 0; c < nv; ++c) colt[c] = c / d->m;
@@ -996,7 +978,7 @@ int tz_problem_create(int device, const tz_problem_desc* d, tz_problem** out) {
   int wgs_per_cu = 1;
   if (p->tt) {
     // ---- tile-triangle class: masks and work plan of the blocked Gram, tile stride, workgroups per CU ----------------------
-    p->ksplit = false; p->chol1 = false;
+    p->ksplit = false;
     p->ntile = Tz * (Tz + 1) / 2;
     const int S = (Kc + 3) / 4;
     // staircase: last non-zero tile column of every super-step, made non-decreasing (it is, when the ordering above is on);
@@ -1071,12 +1053,7 @@ int tz_problem_create(int device, const tz_problem_desc* d, tz_problem** out) {
     TZ_HIP(p->gunits.upload(best_units)); TZ_HIP(p->gunit_ptr.upload(best_ptr));
     p->mfma_gram = (int64_t)best_span; p->mfma_chol = (int64_t)Tz * Tz * Tz / 24; p->mfma_issued = p->mfma_gram * TZ_NWAVES + p->mfma_chol;
   } else {
-    p->ksplit = (p->Tz <= TZ_KS_TZ);
-    p->chol1 = (p->Tz <= 16);
-    if (d->plan_flags & TZ_PLAN_GENERAL_CHOLESKY) p->chol1 = false;
-    if (d->plan_flags & TZ_PLAN_ITEM_GRAM) p->ksplit = false;
-    if (const char* e = tz_dev_getenv("TZ_CHOL1")) { if (e[0] == '0') p->chol1 = false; }
-    if (const char* e = tz_dev_getenv("TZ_KSPLIT")) { if (e[0] == '0') p->ksplit = false; }
+    p->ksplit = (p->Tz <= TZ_KS_TZ) && !(d->plan_flags & TZ_PLAN_ITEM_GRAM);
     p->hsize = (size_t)p->nquads * TZ_QSTR;
     // nz <= 64: the 128-register variant, h and G x of the rows parked in LDS
     p->lds_bytes = tz_ipm_lds_doubles(p->hsize, 0, Tz, nzp, mip, p->nklist, p->ntheta, p->ksplit ? 1 : 0, p->ntube, p->nell, 1) * sizeof(double);
@@ -1092,40 +1069,10 @@ int tz_problem_create(int device, const tz_problem_desc* d, tz_problem** out) {
     if (ttk != p->tt) TZ_FAIL(TZ_ERR_UNSUPPORTED, "kernel class and table format disagree (development build?)");
   }
   TZ_HIP(hipFuncSetAttribute((const void*)p->ipm_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds_bytes));
-  if (const char* e = tz_dev_getenv("TZ_PROF")) { p->prof = (e[0] == '1'); }
-  if (p->prof && !TZ_PROFILE) TZ_FAIL(TZ_ERR_INVALID, "TZ_PROF=1 needs the diagnostic build of the library (libtzddpc_hip_prof.so)");
-  if (const char* e = tz_dev_getenv("TZ_WARM")) { p->warm_enabled = (e[0] != '0'); }
   if (d->plan_flags & TZ_PLAN_UNFUSED) p->fuse_enabled = false;
-  if (const char* e = tz_dev_getenv("TZ_FUSE")) { p->fuse_enabled = (e[0] != '0'); }
   // the tube pass of the fused step keeps |C_K^l e0| (pmax n doubles) in the factor storage, which is free at that point: a short-horizon,
   // large-n problem whose factor is smaller than that runs the four-kernel step instead (tz_tube_kernel has its own scratch)
   if ((size_t)std::max(p->pmax, 1) * p->n > p->hsize) p->fuse_enabled = false;
-  // experiment switches (tools/): the same ranges as the setters (tz_problem_set_stopping / _warm_quiet / _warm_push) -- a value
-  // that does not parse or lies outside fails the create call instead of silently changing the solver's accuracy
-  {
-    auto envd = [](const char* name, double lo, bool lo_open, double hi, double& dst) -> bool {
-      const char* e = tz_dev_getenv(name);
-      if (!e) return true;
-      char* end = nullptr;
-      const double v = strtod(e, &end);
-      if (end == e || *end != '\0' || !(lo_open ? v > lo : v >= lo) || !(v <= hi)) return false;
-      dst = v;
-      return true;
-    };
-    double sq = (double)p->shift_quiet;
-    if (!envd("TZ_SHIFT_QUIET", 0.0, false, 1e9, sq)) TZ_FAIL(TZ_ERR_INVALID, "TZ_SHIFT_QUIET must be an integer >= 0");
-    p->shift_quiet = (int)sq;
-    if (!envd("TZ_WARM_FLOOR", 0.0, true, 1e300, p->warm_floor)) TZ_FAIL(TZ_ERR_INVALID, "TZ_WARM_FLOOR must be > 0");
-    if (!envd("TZ_WARM_GAIN", 0.0, false, 1e300, p->warm_gain)) TZ_FAIL(TZ_ERR_INVALID, "TZ_WARM_GAIN must be >= 0");
-    if (!envd("TZ_WARM_CAP", 0.0, true, 1e300, p->warm_cap) || p->warm_cap < p->warm_floor) TZ_FAIL(TZ_ERR_INVALID, "TZ_WARM_CAP must be >= the floor");
-    if (!envd("TZ_MU_FACTOR", 0.0, true, 1.0, p->mu_factor)) TZ_FAIL(TZ_ERR_INVALID, "TZ_MU_FACTOR must be in (0, 1]");
-    if (!envd("TZ_RES_FACTOR", 1.0, false, 1e300, p->res_factor)) TZ_FAIL(TZ_ERR_INVALID, "TZ_RES_FACTOR must be >= 1");
-    if (!envd("TZ_AFF_THR", 0.0, true, 1.0, p->aff_thr)) TZ_FAIL(TZ_ERR_INVALID, "TZ_AFF_THR must be in (0, 1]");
-    if (!envd("TZ_AFF_MU", 0.0, true, 1.0, p->aff_mu)) TZ_FAIL(TZ_ERR_INVALID, "TZ_AFF_MU must be in (0, 1]");
-    double sf = p->step_frac;
-    if (!envd("TZ_STEP_FRAC", 0.0, true, 1.0, sf) || !(sf < 1.0)) TZ_FAIL(TZ_ERR_INVALID, "TZ_STEP_FRAC must be in (0, 1)");
-    p->step_frac = sf;
-  }
   if (p->prof) { TZ_HIP(p->prof_buf.alloc(PH_COUNT + 16)); TZ_HIP(hipMemset(p->prof_buf.p, 0, (PH_COUNT + 16) * sizeof(unsigned long long))); }
   TZ_HIP(p->work_buf.alloc(3));
   TZ_HIP(hipMemset(p->work_buf.p, 0, 3 * sizeof(unsigned long long)));
@@ -1210,8 +1157,8 @@ static int seed_warm(tz_problem* p, int B) {
 }
 // warm-start state of a closed-loop launch: the previous step's, else the stored start's, else none (cold)
 static int closed_loop_warm(tz_problem* p, int B, bool* warm) {
-  *warm = p->warm_enabled && p->have_prev && p->prevB == B;
-  if (!*warm && p->warm_enabled && p->have_ref) { int rc = seed_warm(p, B); if (rc) return rc; *warm = true; }
+  *warm = p->have_prev && p->prevB == B;
+  if (!*warm && p->have_ref) { int rc = seed_warm(p, B); if (rc) return rc; *warm = true; }
   return TZ_OK;
 }
 
@@ -1328,7 +1275,7 @@ int tz_simulate_batch(tz_problem* p, int32_t B, int32_t T, const double* x0, con
     if (rc) return rc;
   }
   for (int t = 0; t < T && !p->fuse_enabled; ++t) {
-    rc = launch_solve(p, B, p->st_xbar.p, p->st_e.p, p->v.p, p->xbar.p, dcost + t, p->status.p, p->iters.p, nullptr, (size_t)T, p->warm_enabled && (t > 0 || warm0), true);
+    rc = launch_solve(p, B, p->st_xbar.p, p->st_e.p, p->v.p, p->xbar.p, dcost + t, p->status.p, p->iters.p, nullptr, (size_t)T, t > 0 || warm0, true);
     if (rc) return rc;
     rc = launch_plant(p, B, dA, dB, dnoise + (size_t)t * n, (size_t)T * n, p->v.p, p->xbar.p, p->status.p,
                       p->st_x.p, p->st_xbar.p, p->st_e.p, du + (size_t)t * m, (size_t)T * m,
@@ -1434,13 +1381,11 @@ int tz_ipm_plan_info(tz_problem* p, int64_t* mfma_gram_per_iter, int64_t* mfma_c
   return TZ_OK;
 }
 
-int tz_problem_plan_get(tz_problem* p, int32_t* fused, int32_t* one_wave_cholesky, int32_t* superstep_gram, int32_t* staircase, int32_t* toeplitz) {
+int tz_problem_plan_get(tz_problem* p, int32_t* fused, int32_t* superstep_gram, int32_t* staircase) {
   if (!p) TZ_FAIL(TZ_ERR_INVALID, "null problem");
   if (fused) *fused = p->fuse_enabled ? 1 : 0;
-  if (one_wave_cholesky) *one_wave_cholesky = p->chol1 ? 1 : 0;
   if (superstep_gram) *superstep_gram = p->ksplit ? 1 : 0;
   if (staircase) *staircase = p->staircase ? 1 : 0;
-  if (toeplitz) *toeplitz = p->toeplitz ? 1 : 0;
   return TZ_OK;
 }
 
@@ -1458,7 +1403,7 @@ int tz_debug_fetch(tz_problem* p, int32_t b, int what, double* out, int32_t capa
     case 4: src = p->s.p + (size_t)b * p->mi; len = p->mi; break;
     case 5: src = p->lam.p + (size_t)b * p->mi; len = p->mi; break;
     case 6: {   // diagnostic build: per-phase cycle sums of workgroup 0 (as doubles)
-      if (!p->prof) TZ_FAIL(TZ_ERR_INVALID, "profiling build not enabled (TZ_PROF=1 at problem creation)");
+      if (!p->prof) TZ_FAIL(TZ_ERR_INVALID, "per-phase clocks exist only in the diagnostic build of the library (libtzddpc_hip_prof.so)");
       unsigned long long h[PH_COUNT + 16];
       TZ_HIP(hipMemcpy(h, p->prof_buf.p, sizeof(h), hipMemcpyDeviceToHost));
       if (capacity < PH_COUNT + 16) TZ_FAIL(TZ_ERR_INVALID, "capacity too small");

@@ -11,7 +11,7 @@ from typing import Optional
 
 import numpy as np
 
-TZ_ABI_VERSION = 4
+TZ_ABI_VERSION = 5
 TZ_MEM_HOST, TZ_MEM_DEVICE = 0, 1
 TZ_SOLVED, TZ_MAX_ITER, TZ_NUMERICAL, TZ_INFEASIBLE = 0, 1, 2, 3
 
@@ -50,7 +50,7 @@ class ProblemDesc(C.Structure):
 
 
 # tz_problem_desc.plan_flags (include/tzddpc.h): force the general-size code paths (parity tests hold the paths against each other)
-TZ_PLAN_UNFUSED, TZ_PLAN_GENERAL_CHOLESKY, TZ_PLAN_ITEM_GRAM, TZ_PLAN_NO_STAIRCASE, TZ_PLAN_ELL_PRODUCTS = 1, 2, 4, 8, 16
+TZ_PLAN_UNFUSED, TZ_PLAN_ITEM_GRAM, TZ_PLAN_NO_STAIRCASE = 1, 4, 8
 
 
 class GenstackDesc(C.Structure):
@@ -124,7 +124,7 @@ def lib():
     L.tz_timing_get.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     L.tz_ipm_plan_info.argtypes = [vp] + [C.POINTER(C.c_int64)] * 5
     L.tz_ipm_work_get.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    L.tz_problem_plan_get.argtypes = [vp] + [C.POINTER(C.c_int32)] * 5
+    L.tz_problem_plan_get.argtypes = [vp] + [C.POINTER(C.c_int32)] * 3
     L.tz_problem_plan_get.restype = C.c_int
     L.tz_debug_fetch.argtypes = [vp, C.c_int32, C.c_int, vp, C.c_int32]
     for name in ("tz_device_count", "tz_problem_create", "tz_problem_destroy", "tz_problem_set_stream", "tz_problem_sync",
@@ -399,11 +399,10 @@ class Problem:
     def plan_info(self):
         a, b, i, c, d = (C.c_int64(0) for _ in range(5))
         check(lib().tz_ipm_plan_info(self._h, C.byref(a), C.byref(b), C.byref(i), C.byref(c), C.byref(d)), "tz_ipm_plan_info")
-        f = [C.c_int32(0) for _ in range(5)]
+        f = [C.c_int32(0) for _ in range(3)]
         check(lib().tz_problem_plan_get(self._h, *[C.byref(v) for v in f]), "tz_problem_plan_get")
         return dict(mfma_gram_per_iter=a.value, mfma_chol_per_iter=b.value, mfma_issued_per_iter=i.value,
-                    lds_bytes=c.value, patch_bytes=d.value, fused=bool(f[0].value), chol1=bool(f[1].value), ksplit=bool(f[2].value),
-                    staircase=bool(f[3].value), toeplitz=bool(f[4].value))
+                    lds_bytes=c.value, patch_bytes=d.value, fused=bool(f[0].value), ksplit=bool(f[1].value), staircase=bool(f[2].value))
 
     def last_iterations(self, B: int) -> np.ndarray:
         """Interior-point iterations of each trajectory in the last launch (diagnostic)."""
