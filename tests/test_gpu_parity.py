@@ -1568,3 +1568,23 @@ def test_literal_tubes_any_size_instance_against_oracle_zonotope_algebra(built, 
         assert Z1.shape[2] == 1 + G.shape[1]
         np.testing.assert_allclose(Z1[b, :, 0], c, rtol=0, atol=1e-13)
         np.testing.assert_allclose(Z1[b, :, 1:], G, rtol=0, atol=1e-13)
+
+
+from tests.test_host_plan import shim as plan_shim      # noqa: E402,F401  (fixture: the planner compiled for the CPU)
+
+
+@pytest.mark.parametrize("case", ["di_n20", "di_n20_k1", "di_n40"])        # super-step Gram, item plan, tile-triangle
+def test_library_plan_is_the_cpu_tested_plan(built, plan_shim, case):
+    """What the library reports of its plan equals what the planner compiled for the CPU (tests/test_host_plan.py checks that one
+    table by table) makes of the same description."""
+    from tests.test_host_plan import build_plan
+    from tzddpc_amd import TZDDPC
+    ctl, _ = common.gpu_controller(case)
+    info = ctl._native.plan_info()
+    args, _ = TZDDPC._native_args(ctl.qp, {})
+    rc, msg, pl = build_plan(plan_shim, args)
+    assert rc == 0, msg
+    want = dict(mfma_gram_per_iter=pl["mfma_gram"], mfma_chol_per_iter=pl["mfma_chol"], mfma_issued_per_iter=pl["mfma_issued"],
+                lds_bytes=pl["lds_bytes"], patch_bytes=8 * len(pl["Gp"]), fused=bool(pl["fused"]), ksplit=bool(pl["ksplit"]),
+                staircase=bool(pl["staircase"]))
+    assert info == want

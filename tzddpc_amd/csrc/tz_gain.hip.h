@@ -13,9 +13,9 @@
 // matrix lives in registers (accumulation) and in an LDS slab laid out [entry][lane] (dynamic indexing of the QR sweeps; a lane
 // only touches its own column of the slab: bank-conflict free, no barriers inside the QR).
 #pragma once
+#include "tz_layout.h"          // TZ_GN_NMAX (this header is also compiled alone, for the host: tests/native/qr_host.cpp)
 
 #define TZ_GN_TILE 32            // generators per LDS tile (32 x 64 doubles = 16 KB)
-#define TZ_GN_NMAX 8             // n <= 8 (TZ_NMAX)
 
 struct GainParams {
   int S, n, ngen, max_iter;

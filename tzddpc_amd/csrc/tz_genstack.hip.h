@@ -17,8 +17,7 @@
 // tz_genstack_values_kernel writes the generator columns themselves (literal order) for one tube: the Ze[1] of solve() (:377).
 #pragma once
 
-#define TZ_GS_TILE 64            // generators per LDS tile
-#define TZ_GS_CHUNK 1024         // generators per workgroup (host plan)
+#define TZ_GS_TILE 64            // generators per LDS tile (TZ_GS_CHUNK, TZ_GS_NARROW_SUB, GsChunk, GsChunkM: tz_layout.h)
 #ifndef TZ_GS_TILE_DOUBLES
 #define TZ_GS_TILE_DOUBLES 1536  // doubles per shared LDS tile (x 2 buffers); 3072 -> 1536: 130 -> 104 registers, 48 -> 22 KB of LDS, 3 -> 4 waves per SIMD:
                                  // 1.250 -> 1.173 ms at 1024 trajectories (0.54 -> 0.57 of the f64 peak); 768: 1.184 ms
@@ -27,10 +26,6 @@
 #define TZ_GS_GWDIV 16           // narrow kernel: a wave tile is 1 / TZ_GS_GWDIV of the shared tile; smaller tiles = fewer registers and less LDS = more
                                  // waves per SIMD to cover the LDS latency of the A reads (32 trajectories: 4 -> 0.0624 ms, 8 -> 0.0592, 16 -> 0.0587)
 #endif
-#define TZ_GS_NARROW_SUB 2       // narrow kernel (few trajectories): blocks that share a chunk, each streaming its tiles once (measured at 32
-                                 // trajectories, 636 chunks: 1 -> 0.0670 ms, 2 -> 0.0641 ms, 4 -> 0.120 ms: the un-overlapped prologue of short blocks)
-
-struct GsChunk { int seg, src, g0, g1; };        // generators [g0, g1) of the SORTED stack: tube seg, source src (-1 none, 0 e0, 1 + j zeta_j)
 
 struct GenstackParams {
   int B, n, m, N, nseg, nchunk, rec;             // rec = doubles per generator record: n (1 + n + m)
@@ -137,8 +132,6 @@ __global__ __launch_bounds__(256) void tz_genstack_kernel(GenstackParams q) {
 //   * a workgroup covers 256 trajectories (wave w: 64 w .. 64 w + 63, NQ = 4 groups of 16) and every wave walks all generators of
 //     the chunk; few trajectories (the stack is streamed once, the HBM-bound regime) go to tz_genstack_mfma_narrow_kernel below;
 //   * blockIdx -> (chunk, trajectory tile) so that the tiles of one chunk run on the same XCD (shared L2) back to back.
-struct GsChunkM { int seg, src, q0, nq; };       // groups [q0, q0 + nq) of 4 generators each (zero-padded), tube seg, source src
-
 struct GenstackMParams {
   int B, n, m, N, nchunk, ntt, nsub;             // ntt = blocks per chunk: trajectory tiles of 256, or (narrow kernel) nsub sub-ranges of its tiles
   const double* recs;                            // groups of GD = 4 R (P + 1) doubles (R = P: K rows appended by the host; R = n: formed in the kernel)

@@ -16,9 +16,7 @@
 // One wave per data set (the whole problem is (n + m + n) x (T - 1) <= 20 x 399 numbers).
 #pragma once
 
-#define TZ_ID_NMAX 8              // K0: dim_x <= 8, dim_u <= 4 (tile counts below)
-#define TZ_ID_MMAX 4
-#define TZ_ID_PMAX 12            // n + m <= 12
+#define TZ_ID_PMAX 12            // n + m <= 12 (TZ_ID_NMAX = 8, TZ_ID_MMAX = 4: tz_layout.h)
 #define TZ_ID_RT 5               // tile rows of Y = [D; Xp' - c_W]: ceil((12 + 8) / 4)
 #define TZ_ID_CT 3               // tile columns (rows of D)
 

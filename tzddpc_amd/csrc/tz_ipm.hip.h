@@ -14,14 +14,9 @@
 #define TZ_RLEV_CARRY_MAX 2      // diagonal-shift level (1e-6) a warm-started step may inherit from the step before ...
 #define TZ_RLEV_GATE 1e6         // ... from the iteration on whose complementarity is within this factor of the one at which that step broke down
 #define TZ_SEED_VIOL_MAX 0.1     // stored start: largest violation of the new rows (equilibrated) it is still used at
-// H lives in LDS as tile rows of quads (4 column tiles); a quad is 4 matrix rows of 16 doubles padded to TZ_QROW = 17 so
-// that neither the MFMA accumulator access (row-major inside the quad) nor the column access of the factorisation and the
-// triangular solves runs into LDS bank conflicts (row stride 16 doubles = 32 banks collides 4- to 8-way).
-#define TZ_QROW 17
-#define TZ_QSTR (4 * TZ_QROW)
-struct IpmItem { int I0, q0, nq, kptr, klen; };
+// The quad layout of H in LDS (TZ_QROW, TZ_QSTR) and the Gram work item (IpmItem) are in tz_layout.h.
 
-// G in balanced "lane-ELL" form for the matrix-vector products (built by the host, tz_problem_create): the non-zeros of every
+// G in balanced "lane-ELL" form for the matrix-vector products (built by the host, tz_plan_ell in tz_plan.h): the non-zeros of every
 // output (a row of G for G x, a column for G'v) are dealt to as many consecutive virtual lanes as it takes to give every lane
 // at most L entries; entry e of virtual lane v is at [(pass * L + e) * NL + lane] with v = pass * NL + lane (NL = 256 for G x,
 // 192 for G'v: waves 1-3, wave 0 does something else meanwhile).  Every lane walks L entries -- coalesced, no zeros fetched,
@@ -459,7 +454,6 @@ __device__ inline void tz_form_H(const IpmParams& p, double* Hq, const double* w
 // are skipped (wave-uniform bit tests of a host-built mask).  The waves split the work 2 x 2: wave>>1 picks the tile-row
 // range [R0, R1), wave&1 the even / odd super-steps; the partial sums are folded over blk with DPP row rotations and the
 // two halves added through LDS in a fixed order (deterministic).
-#define TZ_KS_TZ 10
 __device__ inline double tz_sel4(int blk, double v0, double v1, double v2, double v3) {
   const double a = (blk & 1) ? v1 : v0, b = (blk & 1) ? v3 : v2;
   return (blk & 2) ? b : a;
@@ -792,20 +786,15 @@ __device__ inline bool tz_fwd_trailing(const IpmParams& p, const double* Hq, con
 }
 
 #include "tz_tt.hip.h"
-// unit size of the blocked Gram by register budget (MINW = workgroups per CU the variant is compiled for: 2 -> 256 registers,
-// 1 -> 512) and super-steps in flight; the host plans its units with the same size (tzddpc_hip.hip)
+// super-steps in flight in the blocked Gram; its unit size TZ_TT_GU(MINW) is in tz_layout.h: the planner (tz_plan_units, tz_plan.h)
+// cuts its units with the same macro
 #define TZ_TT_NST 4
-#define TZ_TT_GU(minw) ((minw) >= 2 ? 6 : 8)
 // triangular solves of the tile-triangle class: by 16 x 16 diagonal blocks with explicit block inverses (default) or tile by tile
 #define TZ_TT_AFTER_CHOL(p, H, dinv) do { tz_tt_block_inverse(p, H, dinv); __syncthreads(); } while (0)
 #define TZ_TT_SOLVE(p, H, dinv, rhs, ybuf, out) tz_chol_solve_blk(p, H, rhs, ybuf, out)
 
-// LDS footprint in doubles (host mirrors this in tzddpc_hip.hip).  hsize: doubles of the factor storage -- nquads * TZ_QSTR in the
-// quad layout (nz <= 64), ntile * TS in the tile-triangle layout; the latter keeps 16 more doubles behind dinv for the factor of
-// the diagonal tile being eliminated (tz_cholesky_tt).
-__host__ __device__ inline size_t tz_ipm_lds_doubles(size_t hsize, int tt, int Tz, int nzp, int mip, int nklist, int ntheta, int ksplit, int ntube, int nell, int park = 0) {
-  return (park ? 2 * (size_t)mip : 0) + (ksplit ? hsize : 0) + hsize + (size_t)Tz * 16 + (tt ? 16 : 0) + 14 * (size_t)nzp + (size_t)(mip + 4) + 32 + 2 + (size_t)((nklist + 1) / 2) + (size_t)ntheta + 4 * TZ_NMAX + (size_t)ntube + (size_t)nell;
-}
+// LDS footprint in doubles: tz_ipm_lds_doubles in tz_layout.h, the one function the kernel below and the planner (tz_plan_place,
+// tz_plan.h) size the dynamic LDS with.
 
 typedef __attribute__((address_space(4))) const IpmParams* TzKargPtr;
 

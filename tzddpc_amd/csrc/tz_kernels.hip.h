@@ -14,19 +14,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "tz_layout.h"     // sizes and record formats shared with the host planner (TZ_THREADS, TZ_NMAX, TzEllEnt, ...)
 
 #ifndef TZ_PROFILE
 #define TZ_PROFILE 0
 #endif
-#define TZ_THREADS 256
-#define TZ_NWAVES 4
-#define TZ_NMAX 16         // max dim_x / dim_u of the MPC path (register arrays of the plant update, LDS slots of the closed-loop state);
-#define TZ_MMAX 8          // K0 (tz_identify.hip.h) and the gain kernels (tz_gain.hip.h) keep their own limits of 8 / 4
 
-// Affine map rows over theta in ELL form: entry e of row r at [e * rows + r] (coalesced over rows), W entries per row, rows
-// with fewer non-zeros padded with (0.0, column 0).  No row pointers: every load of a row is independent of the others.  An entry
-// is one 16-byte record (value, byte offset of the theta entry, zero): one vector-memory instruction per non-zero.
-struct __attribute__((aligned(16))) TzEllEnt { double val; unsigned off; unsigned pad; };
 typedef double tz_d2 __attribute__((ext_vector_type(2)));
 // byte offset of the input entry: both halves of the record's second double are used (the second is zero), so that the record stays
 // ONE 16-byte load (the compiler splits a load of which only 12 bytes are consumed into two); base + off + pad is one v_add3_u32
@@ -34,7 +27,7 @@ __device__ inline unsigned tz_ell_off(double y) {
   const unsigned long long w = __builtin_bit_cast(unsigned long long, y);
   return (unsigned)w + (unsigned)(w >> 32);
 }
-struct TzCsr {
+struct TzCsr {               // affine map rows over theta in ELL form (record format: TzEllEnt, tz_layout.h)
   int rows, W;
   const TzEllEnt* ent;
   const double* c0;
@@ -45,7 +38,7 @@ struct TzCsr {
 //   Z^(0) = <e0>;  Z^(p+1) = M_K Z^(p):  c^(p+1) = C_K c^(p),  beta_p = D_K (|c^(p)| + rad^(p)),
 //   rad^(p+1) = sum_{l<=p} |C_K^(p-l)| beta_l,   radU^(p+1) = sum_{l<=p} |K C_K^(p-l)| beta_l
 // Given a_l = |c^(l)| the recursion is linear with nonnegative coefficients, so its resolvent is a constant of the
-// problem (block lower-triangular Toeplitz, built once on the host in tz_problem_create):
+// problem (block lower-triangular Toeplitz, built once on the host: tz_plan_tube, tz_plan.h):
 //   rad^(p) = sum_{l<p} Tx_{p-1-l} a_l ,  radU^(p) = sum_{l<p} Tu_{p-1-l} a_l ,  c^(l) = C_K^l e0
 // which turns an O(pmax) dependent chain into two short parallel passes.
 // theta = [xbar0 | |xbar0| | (c_k, rho^x_k, rho^u_k) for k < N] with step k taking power[k].
@@ -60,7 +53,6 @@ struct TubeParams {
   int* prestatus;        // B: cleared here, set by tz_affine_kernel when a parameter-only row is violated
 };
 
-#define TZ_PMAX 128        // highest supported power of M_K
 template <int CTRL>
 __device__ inline double tz_quad_xor(double v) {                       // DPP quad_perm of a double (0xB1: lane^1, 0x4E: lane^2)
   const unsigned long long u = __builtin_bit_cast(unsigned long long, v);

@@ -19,11 +19,10 @@ __device__ inline int tz_tri(int I) { return (I * (I + 1)) >> 1; }
 // four blocks of the instruction are four patch rows of the SAME output tile: lane (k, blk, ij) loads element [k][ij] of tile T of
 // patch row 4 s + blk -- one value per (super-step, tile) that serves as the A operand (times w) of tile row T and as the B
 // operand of tile column T -- so a unit costs nr + nc loads per nr * nc MFMAs.  The library orders variables and rows so that the
-// non-zeros of G lie under a staircase (tz_problem_create): a unit is dense on the super-steps [s0, S) and skipped before, no
+// non-zeros of G lie under a staircase (tz_plan_order, tz_plan.h): a unit is dense on the super-steps [s0, S) and skipped before, no
 // per-tile tests in the loop.  The host deals the units to the four waves by their MFMA count.
 // ---------------------------------------------------------------------------------------------------------------------------
-#define TZ_GU 8                  // largest unit any variant uses
-struct TzGUnit { int ib, jb, s0; };     // tile rows [ib, ib + U) x tile columns [jb, jb + U); s0: first super-step that touches tile column ib
+#define TZ_GU 8                  // largest unit any variant uses (TzGUnit, the unit record: tz_layout.h)
 
 template <bool DIAG, int U>
 struct TzGuStage { double vr[U]; double vc[DIAG ? 1 : U]; double w; };

@@ -1,26 +1,19 @@
-// C-ABI of the MI355X TZDDPC hot path (see include/tzddpc.h).  Host side: uploads the problem,
-// packs the constraint matrix into 4x4 MFMA patches, builds the static Gram work plan, launches the
-// kernels of tz_kernels.hip.h on one HIP stream.  No torch types, no CPU compute fallback: every
+// C-ABI of the MI355X TZDDPC hot path (see include/tzddpc.h).  Host side: has tz_plan.h plan the problem
+// (orderings, 4x4 MFMA patches, Gram work plan, ELL tables, LDS placement), uploads the plan's tables and
+// launches the kernels of tz_kernels.hip.h on one HIP stream.  No torch types, no CPU compute fallback: every
 // numeric result comes out of a kernel.
 #include "tz_kernels.hip.h"
+#include "tz_plan.h"
 
 // Neither build of the library reads an environment variable: what a caller may choose goes through tz_problem_desc (plan_flags)
 // and the tz_problem_set_* entry points.  The diagnostic build (libtzddpc_hip_prof.so, -DTZ_PROFILE=1) only adds per-phase clocks.
 #include "../../include/tzddpc.h"
 
-#include <algorithm>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <memory>
-#include <numeric>
-#include <string>
-#include <vector>
 
 static thread_local std::string g_err;
 
-#define TZ_FAIL(code, ...) do { char _b[512]; snprintf(_b, sizeof(_b), __VA_ARGS__); g_err = _b; return (code); } while (0)
+#define TZ_FAIL(code, ...) TZ_FAIL_TO(g_err, code, __VA_ARGS__)
 #define TZ_HIP(call) do { hipError_t _e = (call); if (_e != hipSuccess) { \
     char _b[512]; snprintf(_b, sizeof(_b), "%s failed: %s (%s:%d)", #call, hipGetErrorString(_e), __FILE__, __LINE__); \
     g_err = _b; return TZ_ERR_HIP; } } while (0)
@@ -44,72 +37,32 @@ struct DevBuf {
     return hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice);
   }
   hipError_t upload(const std::vector<T>& v) { return upload(v.data(), v.size()); }
-  void swap(DevBuf& o) { std::swap(p, o.p); std::swap(n, o.n); }
   DevBuf() = default;
   DevBuf(const DevBuf&) = delete;
   DevBuf& operator=(const DevBuf&) = delete;
 };
 
-// Balanced lane-ELL of a sparse matrix for the matrix-vector products of tz_ipm_kernel (TzEll in tz_ipm.hip.h).
-// outs[o] = (index, value) pairs of output o; NL physical lanes per pass; the virtual lane count VL is a multiple of NL.
-// compact: 8-byte values and 16-bit indices in two arrays (the tile-triangle class, see TzEll) instead of 16-byte records.
+// device copy of a lane-ELL table of the plan (TzEll in tz_ipm.hip.h)
 struct DevEll {
   DevBuf<TzEllEnt> ent; DevBuf<int> seg; DevBuf<double> val; DevBuf<unsigned short> idx;
   int L = 1, VL = 0;
-  hipError_t build(const std::vector<std::vector<std::pair<int, double>>>& outs, int NL, int VLwant, bool compact) {
-    VL = ((std::max(VLwant, 1) + NL - 1) / NL) * NL;
-    size_t longest = 1;
-    for (auto& o : outs) longest = std::max(longest, o.size());
-    for (L = 1; L <= (int)longest; ++L) {
-      size_t lanes = 0;
-      for (auto& o : outs) lanes += (o.size() + L - 1) / L;
-      if (lanes <= (size_t)VL) break;
-    }
-    std::vector<TzEllEnt> v(compact ? 0 : (size_t)VL * L, TzEllEnt{0.0, 0u, 0u});
-    std::vector<double> cv(compact ? (size_t)VL * L : 0, 0.0);
-    std::vector<unsigned short> ci(compact ? (size_t)VL * L : 0, (unsigned short)0);
-    std::vector<int> sg(std::max<size_t>(outs.size(), 1), 0);
-    int lane = 0;
-    for (size_t o = 0; o < outs.size(); ++o) {
-      const int cnt = (int)((outs[o].size() + L - 1) / L);
-      sg[o] = lane | (cnt << 16);
-      for (size_t e = 0; e < outs[o].size(); ++e) {
-        const int vl = lane + (int)(e / L), slot = (int)(e % L);
-        const size_t pos = ((size_t)(vl / NL) * L + slot) * NL + (vl % NL);
-        if (compact) { cv[pos] = outs[o][e].second; ci[pos] = (unsigned short)outs[o][e].first; }
-        else v[pos] = TzEllEnt{outs[o][e].second, (unsigned)outs[o][e].first * 8u, 0u};
-      }
-      lane += cnt;
-    }
+  hipError_t upload(const TzEllTable& t) {
+    L = t.L; VL = t.VL;
     hipError_t e;
-    if (compact) {
-      if ((e = val.upload(cv)) != hipSuccess) return e;
-      if ((e = idx.upload(ci)) != hipSuccess) return e;
-    } else if ((e = ent.upload(v)) != hipSuccess) return e;
-    return seg.upload(sg);
+    if ((e = ent.upload(t.ent)) != hipSuccess || (e = val.upload(t.val)) != hipSuccess || (e = idx.upload(t.idx)) != hipSuccess) return e;
+    return seg.upload(t.seg);
   }
   TzEll view() const { return TzEll{L, VL, ent.p, seg.p, val.p, idx.p}; }
-  void swap(DevEll& o) { ent.swap(o.ent); seg.swap(o.seg); val.swap(o.val); idx.swap(o.idx); std::swap(L, o.L); std::swap(VL, o.VL); }
 };
 
-struct DevCsr {          // device copy of a tz_affmap (CSR in the ABI) re-laid out as ELL, see TzCsr
+struct DevCsr {          // device copy of an affine map of the plan (TzCsr)
   DevBuf<TzEllEnt> ent;
   DevBuf<double> c0;
   int rows = 0, W = 1;
-  // perm (may be null): device row i is row perm[i] of the map
-  hipError_t upload(const tz_affmap& m, const int* perm = nullptr) {
-    rows = m.rows; W = 1;
-    for (int r = 0; r < m.rows; ++r) W = std::max(W, m.ptr[r + 1] - m.ptr[r]);
-    std::vector<TzEllEnt> ve((size_t)W * std::max(rows, 1), TzEllEnt{0.0, 0u, 0u});
-    std::vector<double> cc((size_t)std::max(rows, 1), 0.0);
-    for (int i = 0; i < m.rows; ++i) {
-      const int r = perm ? perm[i] : i;
-      cc[i] = m.c0[r];
-      for (int e = m.ptr[r]; e < m.ptr[r + 1]; ++e) ve[(size_t)(e - m.ptr[r]) * rows + i] = TzEllEnt{m.val[e], (unsigned)m.col[e] * 8u, 0u};
-    }
-    hipError_t e;
-    if ((e = ent.upload(ve)) != hipSuccess) return e;
-    return c0.upload(cc.data(), (size_t)m.rows);
+  hipError_t upload(const TzMapTable& t) {
+    rows = t.rows; W = t.W;
+    hipError_t e = ent.upload(t.ent);
+    return e != hipSuccess ? e : c0.upload(t.c0);
   }
   TzCsr view() const { return TzCsr{rows, W, ent.p, c0.p}; }
 };
@@ -126,16 +79,16 @@ template <int R> ipm_fn_t ipm_pick_tt(int ncg, int w) {
   if (w >= 2) { switch (ncg) { case 1: case 2: return tz_ipm_kernel<R, 2, 2>; case 3: return tz_ipm_kernel<R, 3, 2>; default: return tz_ipm_kernel<R, 4, 2>; } }
   switch (ncg) { case 1: case 2: return tz_ipm_kernel<R, 2, 1>; case 3: return tz_ipm_kernel<R, 3, 1>; default: return tz_ipm_kernel<R, 4, 1>; }
 }
-// tt (out): the variant uses the tile-triangle layout
-ipm_fn_t ipm_kernel_for(int maxr, int ncg, int wgs_per_cu, bool& tt) {
+// The variant for a plan (tt: the plan's class); null when a development build does not carry it, TZ_NO_VARIANT says why.
+ipm_fn_t ipm_kernel_for(int maxr, int ncg, int wgs_per_cu, bool tt) {
 #ifdef TZ_ONLY_SMALL      // development builds (assembly study, quick A/B of the bench problem): only the variant for mi <= 256, nz <= 64
-  tt = false;
+  (void)wgs_per_cu; (void)tt;
   return (maxr == 1 && ncg == 1) ? tz_ipm_kernel<1, 1, TZ_MINWAVES> : nullptr;
 #elif defined(TZ_ONLY_TT)  // development builds of the tile-triangle class: -DTZ_ONLY_TT=R,NCG,W  (one variant, seconds to build)
-  tt = true; (void)wgs_per_cu;
-  return tz_ipm_kernel<TZ_ONLY_TT>;
+#define TZ_NO_VARIANT "kernel class and table format disagree (development build?)"
+  (void)maxr; (void)ncg; (void)wgs_per_cu;
+  return tt ? tz_ipm_kernel<TZ_ONLY_TT> : nullptr;
 #else
-  tt = (ncg >= 2 || maxr > 4);
   if (!tt) {
     switch (maxr) { case 1: return tz_ipm_kernel<1, 1, TZ_MINWAVES>; case 2: return tz_ipm_kernel<2, 1, TZ_MINWAVES>; case 3: return tz_ipm_kernel<3, 1, TZ_MINWAVES>; default: return tz_ipm_kernel<4, 1, TZ_MINWAVES>; }
   }
@@ -147,17 +100,30 @@ ipm_fn_t ipm_kernel_for(int maxr, int ncg, int wgs_per_cu, bool& tt) {
   }
 #endif
 }
+#ifndef TZ_NO_VARIANT
+#define TZ_NO_VARIANT "this development build (TZ_ONLY_SMALL) carries only the mi <= 256, nz <= 64 kernel"
+#endif
+
+// "use this device": the entry points that take a device number start with it
+int use_device(int device) {
+  int ndev = 0;
+  TZ_HIP(hipGetDeviceCount(&ndev));
+  if (ndev <= 0) TZ_FAIL(TZ_ERR_HIP, "no HIP device visible: the TZDDPC hot path has no CPU fallback");
+  if (device < 0 || device >= ndev) TZ_FAIL(TZ_ERR_INVALID, "device %d out of range (0..%d)", device, ndev - 1);
+  TZ_HIP(hipSetDevice(device));
+  return TZ_OK;
+}
 
 }  // namespace
 
 struct tz_problem {
   int device = 0;
   int n = 0, m = 0, N = 0, nz = 0, mi = 0, ntheta = 0, npar = 0, nc_rows = 0, pmax = 0;
-  int nzp = 0, mip = 0, Tz = 0, Kc = 0, nquads = 0, nklist = 0, nP = 0;
+  TzPlanSizes pl;              // derived sizes and decisions of the plan (tz_plan.h)
   int max_iter = 40;
   double tol = 1e-10, reg = 1e-12, step_frac = 0.99, cost_scale = 1.0, r0 = 0.0;
   // constants
-  DevBuf<double> P, G, Gt, Gp, act_scale, Dz, Phi, Gam, r1, R2, CK, DK, K, CKpow, Ttube, par_lo, par_hi, rec0, recx, recy;
+  DevBuf<double> P, Gp, act_scale, Dz, Phi, Gam, r1, R2, CK, DK, K, CKpow, Ttube, par_lo, par_hi, rec0, recx, recy;
   DevBuf<int> power, row_of, klist, item_ptr, smask, shift_var, shift_row;
   DevBuf<double> shift_xs, shift_ls;
   int shift_policy = 0;        // 0 never, 1 always, k >= 2: after a step of >= k iterations (tz_problem_set_warm_shift)
@@ -166,9 +132,6 @@ struct tz_problem {
   DevBuf<IpmItem> items;
   DevCsr q, h, par;
   DevEll eg, et;
-  int nell = 0;
-  size_t lds_bytes = 0;
-  int64_t mfma_gram = 0, mfma_chol = 0, mfma_issued = 0;
   // workspace (capacity Bcap)
   int Bcap = 0;
   DevBuf<double> theta, qv, hv, x, s, lam, v, xbar, cost, in_x0, in_e0;
@@ -190,20 +153,12 @@ struct tz_problem {
   DevBuf<double> ref_x, ref_lam;          // stored start (tz_problem_store_start): solution and multipliers of one reference solve
   bool have_ref = false;
   double warm_floor = 1e-8, warm_gain = 1.0, warm_cap = 1e300, mu_factor = 1e-3, res_factor = 100.0;
-  int ntube = 0;
-  bool tt = false;             // tile-triangle layout / blocked Gram / two-phase Cholesky (nz > 64 or more than 1024 rows)
-  int TS = 16, ntile = 0, gu = 0;
-  size_t hsize = 0;            // doubles of factor storage in LDS
   DevBuf<TzGUnit> gunits; DevBuf<int> gunit_ptr;
   DevBuf<int> vpos;            // staircase ordering (tile-triangle class): device position of v[k, j]; null = identity
-  std::vector<int> permc, permr;   // device variable / row i is the caller's permc[i] / permr[i] (empty = identity)
-  bool ksplit = false;         // Gram by k-split (Tz <= TZ_KS_TZ; TZ_PLAN_ITEM_GRAM keeps the item plan)
-  bool fuse_enabled = true;    // closed-loop steps in one launch (TZ_PLAN_UNFUSED: four kernels per step, same arithmetic)
-  bool staircase = false;      // tile-triangle class: variables in time order, rows by last non-zero column (library-internal)
-  bool lean_epilogue = false;  // FuseParams::lean_epilogue
+  std::vector<int> permc, permr;   // device variable / row i is the caller's permc[i] / permr[i] (identity without the staircase ordering)
+  bool fuse_enabled = true;    // pl.fused, until a tube stack is attached
   struct tz_genstack* tube_stack = nullptr;   // literal problems: decision-independent generators, evaluated per solve (not owned)
   DevBuf<double> ts_zeta, ts_c, ts_rx, ts_ru;  int ts_cap = 0;
-  int maxr = 1, ncg = 1;
   void (*ipm_fn)(IpmParams) = nullptr;
   DevBuf<unsigned long long> prof_buf, work_buf;
 };
@@ -279,16 +234,16 @@ void drain_timing(tz_problem* p) {
 
 IpmParams ipm_params(tz_problem* p, int B, int* d_status, int* d_iters, bool warm, bool track_prev) {
   IpmParams ip{};
-  ip.B = B; ip.nz = p->nz; ip.mi = p->mi; ip.nzp = p->nzp; ip.mip = p->mip; ip.Tz = p->Tz; ip.Kc = p->Kc; ip.nquads = p->nquads;
-  ip.P = p->P.p; ip.Gp = p->Gp.p; ip.items = p->items.p; ip.item_ptr = p->item_ptr.p; ip.klist = p->klist.p; ip.smask = p->smask.p; ip.eg = p->eg.view(); ip.et = p->et.view(); ip.nell = p->nell;
+  ip.B = B; ip.nz = p->nz; ip.mi = p->mi; ip.nzp = p->pl.nzp; ip.mip = p->pl.mip; ip.Tz = p->pl.Tz; ip.Kc = p->pl.Kc; ip.nquads = p->pl.nquads;
+  ip.P = p->P.p; ip.Gp = p->Gp.p; ip.items = p->items.p; ip.item_ptr = p->item_ptr.p; ip.klist = p->klist.p; ip.smask = p->smask.p; ip.eg = p->eg.view(); ip.et = p->et.view(); ip.nell = p->pl.nell;
   ip.q = p->qv.p; ip.h = p->hv.p; ip.prestatus = p->prestatus.p; ip.x = p->x.p; ip.s = p->s.p; ip.lam = p->lam.p;
   ip.status = d_status; ip.iters = d_iters ? d_iters : p->iters.p;
   ip.max_iter = p->max_iter; ip.tol = p->tol; ip.reg = p->reg; ip.step_frac = p->step_frac; ip.mu_tol = p->tol * p->mu_factor; ip.tol_res = p->tol * p->res_factor;
   ip.inv_mi = 1.0 / p->mi; ip.mu_floor = 1e-3 * ip.mu_tol; ip.tol_loose = 1e3 * p->tol; ip.step_frac_retry = std::min(p->step_frac, 0.99);
   ip.prof = p->prof ? p->prof_buf.p : nullptr;
   ip.work = p->timing ? p->work_buf.p : nullptr;
-  ip.TS = p->TS; ip.ntile = p->ntile; ip.gu = p->gu; ip.gunits = p->gunits.p; ip.gunit_ptr = p->gunit_ptr.p;
-  ip.nklist = p->nklist; ip.nP = p->nP; ip.ksplit = p->ksplit ? 1 : 0; ip.ntube = p->ntube;
+  ip.TS = p->pl.TS; ip.ntile = p->pl.ntile; ip.gu = p->pl.gu; ip.gunits = p->gunits.p; ip.gunit_ptr = p->gunit_ptr.p;
+  ip.nklist = p->pl.nklist; ip.nP = p->pl.nP; ip.ksplit = p->pl.ksplit ? 1 : 0; ip.ntube = p->pl.ntube;
   ip.shift_policy = p->have_shift ? p->shift_policy : 0; ip.shift_quiet = p->shift_quiet;
   ip.shift_state = p->shift_state.p;
   ip.sx = p->shift_var.p; ip.sr = p->shift_row.p; ip.sxs = p->shift_xs.p; ip.sls = p->shift_ls.p;
@@ -311,18 +266,18 @@ int launch_step_fused(tz_problem* p, int B, double* d_x, double* d_xbar, double*
   Timer tm(p, K_IPM);
   IpmParams ip = ipm_params(p, B, d_status, p->iters.p, warm, true);
   FuseParams& F = ip.F;
-  F.on = 1; F.npar = p->npar; F.ntheta = p->ntheta; F.lean_epilogue = p->lean_epilogue ? 1 : 0; F.sticky_fresh = sticky_fresh ? 1 : 0;
+  F.on = 1; F.npar = p->npar; F.ntheta = p->ntheta; F.lean_epilogue = p->pl.lean_epilogue ? 1 : 0; F.sticky_fresh = sticky_fresh ? 1 : 0;
   F.nsteps = nsteps; F.warm_steps = 1; ip.warm_steps = F.warm_steps;
   F.w_step = ss.w; F.u_step = ss.u; F.x_step = ss.x; F.cost_step = ss.cost;
   F.tube = TubeParams{B, p->n, p->m, p->N, p->pmax, p->ntheta, p->CKpow.p, p->Ttube.p, p->power.p, d_xbar, d_e, nullptr, nullptr};
   F.qmap = p->q.view(); F.hmap = p->h.view(); F.parmap = p->par.view(); F.par_lo = p->par_lo.p; F.par_hi = p->par_hi.p;
-  F.fin = FinishParams{B, p->n, p->m, p->N, p->nz, p->mi, p->nzp, p->nc_rows, p->P.p, p->Dz.p, p->Phi.p, p->Gam.p,
+  F.fin = FinishParams{B, p->n, p->m, p->N, p->nz, p->mi, p->pl.nzp, p->nc_rows, p->P.p, p->Dz.p, p->Phi.p, p->Gam.p,
                        p->r1.p, p->R2.p, p->r0, p->cost_scale, p->row_of.p, p->act_scale.p, d_xbar, nullptr, nullptr, nullptr, nullptr,
                        d_status, nsteps > 1 ? nullptr : p->v.p, nsteps > 1 ? nullptr : p->xbar.p, d_cost, nullptr, cost_stride, p->vpos.p,
                        p->rec0.p, p->recx.p, p->recy.p};
   F.plant = PlantParams{B, p->n, p->m, p->N, p->K.p, d_A, d_Bm, nullptr, nullptr, d_w, w_stride, d_status, d_x, d_xbar, d_e,
                         d_u, u_stride, d_xout, x_stride, d_sticky};
-  hipLaunchKernelGGL(p->ipm_fn, dim3(B), dim3(TZ_THREADS), p->lds_bytes, p->stream, ip);
+  hipLaunchKernelGGL(p->ipm_fn, dim3(B), dim3(TZ_THREADS), p->pl.lds_bytes, p->stream, ip);
   TZ_HIP(hipGetLastError());
   return TZ_OK;
 }
@@ -349,11 +304,11 @@ int launch_solve(tz_problem* p, int B, const double* d_xbar0, const double* d_e0
     // stopping target, but never below 1e-6 tol (1e-16 at the default tolerance: what the loosest calibrated target used to give --
     // with the tighter targets of round 3 an unbounded 1e-3 asked degenerate problems for mu = 1e-18 and they ended TZ_NUMERICAL)
     if (d_active) { const double f = std::min(1.0, std::max(1e-3, 1e-6 * p->tol / ip.mu_tol)); ip.mu_tol *= f; ip.mu_floor *= f; }
-    hipLaunchKernelGGL(p->ipm_fn, dim3(B), dim3(TZ_THREADS), p->lds_bytes, st, ip);
+    hipLaunchKernelGGL(p->ipm_fn, dim3(B), dim3(TZ_THREADS), p->pl.lds_bytes, st, ip);
   }
   {
     Timer tm(p, K_FINISH);
-    FinishParams fp{B, p->n, p->m, p->N, p->nz, p->mi, p->nzp, p->nc_rows, p->P.p, p->Dz.p, p->Phi.p, p->Gam.p,
+    FinishParams fp{B, p->n, p->m, p->N, p->nz, p->mi, p->pl.nzp, p->nc_rows, p->P.p, p->Dz.p, p->Phi.p, p->Gam.p,
                     p->r1.p, p->R2.p, p->r0, p->cost_scale, p->row_of.p, p->act_scale.p, d_xbar0, p->qv.p, p->x.p, p->s.p, p->lam.p,
                     d_status, d_v, d_xbar, d_cost, d_active, cost_stride, p->vpos.p, p->rec0.p, p->recx.p, p->recy.p};
     hipLaunchKernelGGL(tz_finish_kernel, dim3(B), dim3(64), 0, st, fp);
@@ -394,11 +349,7 @@ int tz_identify_batch(int device, int32_t B, int32_t T, int32_t n, int32_t m, co
   if (n < 1 || n > TZ_ID_NMAX || m < 1 || m > TZ_ID_MMAX) TZ_FAIL(TZ_ERR_UNSUPPORTED, "identification on the device (K0): dim_x must be 1..%d and dim_u 1..%d", TZ_ID_NMAX, TZ_ID_MMAX);
   if (K && (!sK || !CK)) TZ_FAIL(TZ_ERR_INVALID, "sK and CK are required when K is given");
   if (mem != TZ_MEM_HOST && mem != TZ_MEM_DEVICE) TZ_FAIL(TZ_ERR_INVALID, "mem must be TZ_MEM_HOST or TZ_MEM_DEVICE");
-  int ndev = 0;
-  TZ_HIP(hipGetDeviceCount(&ndev));
-  if (ndev <= 0) TZ_FAIL(TZ_ERR_HIP, "no HIP device visible: the TZDDPC hot path has no CPU fallback");
-  if (device < 0 || device >= ndev) TZ_FAIL(TZ_ERR_INVALID, "device %d out of range (0..%d)", device, ndev - 1);
-  TZ_HIP(hipSetDevice(device));
+  if (int rc = use_device(device)) return rc;
   const int p = n + m;
   const size_t b = (size_t)B;
   IdentifyParams q{B, T, n, m, u, x, w_center, K, k_shared ? 1 : 0, C, s, K ? sK : nullptr, K ? CK : nullptr, status};
@@ -427,11 +378,7 @@ static int gain_batch(bool adversary, int device, int32_t S, int32_t n, int32_t 
   if (S <= 0 || ngen < 0) TZ_FAIL(TZ_ERR_INVALID, "S must be positive, ngen non-negative");
   if (n < 1 || n > TZ_GN_NMAX) TZ_FAIL(TZ_ERR_UNSUPPORTED, "dim_x must be 1..%d", TZ_GN_NMAX);
   if (adversary && max_iter < 1) TZ_FAIL(TZ_ERR_INVALID, "max_iter must be positive");
-  int ndev = 0;
-  TZ_HIP(hipGetDeviceCount(&ndev));
-  if (ndev <= 0) TZ_FAIL(TZ_ERR_HIP, "no HIP device visible: the TZDDPC hot path has no CPU fallback");
-  if (device < 0 || device >= ndev) TZ_FAIL(TZ_ERR_INVALID, "device %d out of range (0..%d)", device, ndev - 1);
-  TZ_HIP(hipSetDevice(device));
+  if (int rc = use_device(device)) return rc;
   const size_t s = (size_t)S, g = (size_t)ngen, n2 = (size_t)n * n;
   DevBuf<double> dM0, dH, dbeta, dbout, dval; DevBuf<int> daux;
   TZ_HIP(dM0.upload(M0, n2));
@@ -475,103 +422,23 @@ struct tz_genstack {
 };
 
 int tz_genstack_create(int device, const tz_genstack_desc* d, tz_genstack** out) {
-  if (!d || !out || !d->seg_ptr || !d->src || !d->m0 || !d->M || !d->c0 || !d->cE || !d->K) TZ_FAIL(TZ_ERR_INVALID, "null argument");
-  if (d->n < 1 || d->n > TZ_NMAX || d->m < 1 || d->m > TZ_MMAX) TZ_FAIL(TZ_ERR_UNSUPPORTED, "dim_x must be 1..%d and dim_u 1..%d", TZ_NMAX, TZ_MMAX);
-  if (d->N < 1 || d->nseg < 1) TZ_FAIL(TZ_ERR_INVALID, "N and nseg must be positive");
-  int ndev = 0;
-  TZ_HIP(hipGetDeviceCount(&ndev));
-  if (ndev <= 0) TZ_FAIL(TZ_ERR_HIP, "no HIP device visible: the TZDDPC hot path has no CPU fallback");
-  if (device < 0 || device >= ndev) TZ_FAIL(TZ_ERR_INVALID, "device %d out of range (0..%d)", device, ndev - 1);
-  TZ_HIP(hipSetDevice(device));
+  if (!d || !out) TZ_FAIL(TZ_ERR_INVALID, "null argument");
+  int rc = tz_genstack_plan_check(*d, g_err);
+  if (rc || (rc = use_device(device))) return rc;
+  TzGenstackPlan plan;
+  if ((rc = tz_genstack_plan_build(*d, plan, g_err))) return rc;
   std::unique_ptr<tz_genstack> g(new tz_genstack());
-  const int n = d->n, m = d->m, p = n + m, rec = n * (1 + p);
-  g->device = device; g->n = n; g->m = m; g->N = d->N; g->nseg = d->nseg; g->rec = rec;
+  const size_t n = d->n, m = d->m, p = n + m;
+  g->device = device; g->n = d->n; g->m = d->m; g->N = d->N; g->nseg = d->nseg; g->rec = plan.rec;
   g->seg_ptr.assign(d->seg_ptr, d->seg_ptr + d->nseg + 1);
-  const int64_t G = g->seg_ptr[d->nseg];
-  g->G = G;
-  for (int64_t i = 0; i < G; ++i) if (d->src[i] < -1 || d->src[i] > d->N) TZ_FAIL(TZ_ERR_INVALID, "src[%lld] out of range", (long long)i);
-  // records [m0 | M]: literal order (tz_genstack_values) and sorted by (tube, source) + cut into chunks (tz_genstack_intervals)
-  std::vector<double> lit((size_t)std::max<int64_t>(G, 1) * rec, 0.0), srt(lit.size(), 0.0);
-  auto fill = [&](double* dst, int64_t gi) {
-    for (int i = 0; i < n; ++i) { dst[i] = d->m0[(size_t)gi * n + i]; for (int c = 0; c < p; ++c) dst[n + i * p + c] = d->M[((size_t)gi * n + i) * p + c]; }
-  };
-  for (int64_t gi = 0; gi < G; ++gi) fill(&lit[(size_t)gi * rec], gi);
-  std::vector<GsChunk> chunks; std::vector<int> scp((size_t)d->nseg + 1, 0);
-  int64_t pos = 0;
-  for (int k = 0; k < d->nseg; ++k) {
-    std::vector<int64_t> idx;
-    for (int64_t gi = g->seg_ptr[k]; gi < g->seg_ptr[k + 1]; ++gi) idx.push_back(gi);
-    std::stable_sort(idx.begin(), idx.end(), [&](int64_t a, int64_t b2) { return d->src[a] < d->src[b2]; });
-    size_t a = 0;
-    while (a < idx.size()) {
-      size_t b2 = a;
-      while (b2 < idx.size() && d->src[idx[b2]] == d->src[idx[a]] && b2 - a < TZ_GS_CHUNK) ++b2;
-      chunks.push_back(GsChunk{k, d->src[idx[a]], (int)pos, (int)(pos + (int64_t)(b2 - a))});
-      for (size_t e = a; e < b2; ++e) fill(&srt[(size_t)pos++ * rec], idx[e]);
-      a = b2;
-    }
-    scp[k + 1] = (int)chunks.size();
-  }
-  g->nchunk = (int)chunks.size();
-  // matrix-core layout of the sorted stack (dimensions with a compiled instance): per group of 4 generators (a chunk is padded
-  // with zero generators) [component c < P][generator i < 4][inner k < P] of Mext = [M; K M], then [c][i] of m0ext = [m0; K m0]
-  g->mfma = (p >= 3 && p <= 7);
-  // one input (the reference's systems): a second copy of the stack holds only the n rows [m0 | M] -- 1 / (n + 1) fewer bytes and matrix
-  // instructions -- and K g is formed in the kernel; it serves every batch except 33 .. 64 trajectories, where the extra vector
-  // arithmetic of the narrow kernel costs more than the rows save (measured: LAB_NOTEBOOK.md, "K g formed in the kernel").
-  g->rows_mf = (m == 1) ? n : p;
-  if (g->mfma && !chunks.empty()) {
-    std::vector<GsChunkM> cm;
-    std::vector<double> ext((size_t)p * (p + 1));
-    auto layout = [&](int RW, std::vector<double>& mf, bool want_chunks) {
-      const int GD = 4 * RW * (p + 1);
-      for (const GsChunk& ch : chunks) {
-        const int ng = ch.g1 - ch.g0, nq = (ng + 3) / 4;
-        const size_t q0 = mf.size() / GD;
-        mf.resize(mf.size() + (size_t)nq * GD, 0.0);
-        for (int gi = 0; gi < ng; ++gi) {
-          const double* r = &srt[(size_t)(ch.g0 + gi) * rec];            // [m0 (n) | M (n x p)]
-          for (int c = 0; c < RW; ++c) {
-            double m0e = 0.0;
-            if (c < n) m0e = r[c]; else for (int i = 0; i < n; ++i) m0e += d->K[(size_t)(c - n) * n + i] * r[i];
-            ext[(size_t)c * (p + 1)] = m0e;
-            for (int k = 0; k < p; ++k) {
-              double v = 0.0;
-              if (c < n) v = r[n + c * p + k]; else for (int i = 0; i < n; ++i) v += d->K[(size_t)(c - n) * n + i] * r[n + i * p + k];
-              ext[(size_t)c * (p + 1) + 1 + k] = v;
-            }
-          }
-          double* gb = &mf[(q0 + gi / 4) * GD];
-          const int i4 = gi & 3;
-          for (int c = 0; c < RW; ++c) {
-            for (int k = 0; k < p; ++k) gb[c * 4 * p + i4 * p + k] = ext[(size_t)c * (p + 1) + 1 + k];
-            gb[4 * RW * p + 4 * c + i4] = ext[(size_t)c * (p + 1)];
-          }
-        }
-        if (want_chunks) cm.push_back(GsChunkM{ch.seg, ch.src, (int)q0, nq});       // group offsets are the same in both layouts
-      }
-    };
-    std::vector<double> mf;
-    layout(p, mf, true);
-    for (double v : mf) if (!std::isfinite(v)) TZ_FAIL(TZ_ERR_INVALID, "non-finite generator entry");
-    TZ_HIP(g->recs_mf.upload(mf)); TZ_HIP(g->chunks_m.upload(cm));
-    if (g->rows_mf != p) {
-      std::vector<double> mfn;
-      layout(g->rows_mf, mfn, false);
-      TZ_HIP(g->recs_mfn.upload(mfn));
-    }
-  }
-  TZ_HIP(g->recs_lit.upload(lit)); TZ_HIP(g->recs_sorted.upload(srt));
-  TZ_HIP(g->src_lit.upload(d->src, (size_t)std::max<int64_t>(G, 1)));
-  if (chunks.empty()) chunks.push_back(GsChunk{0, -1, 0, 0});
-  TZ_HIP(g->chunks.upload(chunks)); TZ_HIP(g->seg_chunk_ptr.upload(scp));
+  g->G = plan.G; g->nchunk = plan.nchunk; g->mfma = plan.mfma; g->rows_mf = plan.rows_mf; g->have_cZ = plan.have_cZ;
+  TZ_HIP(g->recs_mf.upload(plan.mf)); TZ_HIP(g->chunks_m.upload(plan.chunks_m)); TZ_HIP(g->recs_mfn.upload(plan.mfn));
+  TZ_HIP(g->recs_lit.upload(plan.lit)); TZ_HIP(g->recs_sorted.upload(plan.srt));
+  TZ_HIP(g->src_lit.upload(d->src, (size_t)std::max<int64_t>(plan.G, 1)));
+  TZ_HIP(g->chunks.upload(plan.chunks)); TZ_HIP(g->seg_chunk_ptr.upload(plan.seg_chunk_ptr));
   TZ_HIP(g->c0.upload(d->c0, (size_t)d->nseg * n)); TZ_HIP(g->cE.upload(d->cE, (size_t)d->nseg * n * n));
-  if (d->cZ) {
-    const size_t cnt = (size_t)d->nseg * d->N * n * p;
-    for (size_t i = 0; i < cnt && !g->have_cZ; ++i) if (d->cZ[i] != 0.0) g->have_cZ = true;
-    if (g->have_cZ) TZ_HIP(g->cZ.upload(d->cZ, cnt));
-  }
-  TZ_HIP(g->K.upload(d->K, (size_t)m * n));
+  if (plan.have_cZ) TZ_HIP(g->cZ.upload(d->cZ, (size_t)d->nseg * d->N * n * p));
+  TZ_HIP(g->K.upload(d->K, m * n));
   TZ_HIP(hipEventCreate(&g->ev0)); TZ_HIP(hipEventCreate(&g->ev1));
   *out = g.release();
   return TZ_OK;
@@ -605,6 +472,13 @@ int gs_inputs(tz_genstack* g, int B, const double* e0, const double* zeta, int m
   return TZ_OK;
 }
 }  // namespace
+
+// room for the per-(chunk, trajectory) partial sums of gs_eval at batch size B (the narrow kernel writes TZ_GS_NARROW_SUB of them)
+static int gs_reserve_partial(tz_genstack* g, int B) {
+  const size_t need = (size_t)std::max(g->nchunk, 1) * (B <= 64 ? TZ_GS_NARROW_SUB : 1) * B * (g->n + g->m);
+  if (need > g->pcap) { TZ_HIP(g->partial.alloc(need)); g->pcap = need; }
+  return TZ_OK;
+}
 
 // evaluation of the whole stack for B trajectories, device pointers, on `st`
 static int gs_eval(tz_genstack* g, int B, const double* de0, const double* dz, double* dc, double* drx, double* dru, hipStream_t st) {
@@ -670,7 +544,7 @@ int tz_genstack_intervals(tz_genstack* g, int32_t B, const double* e0, const dou
   const double *de0 = nullptr, *dz = nullptr;
   int rc = gs_inputs(g, B, e0, zeta, mem, &de0, &dz);
   if (rc) return rc;
-  { const size_t need = (size_t)std::max(g->nchunk, 1) * (B <= 64 ? TZ_GS_NARROW_SUB : 1) * B * p; if (need > g->pcap) { TZ_HIP(g->partial.alloc(need)); g->pcap = need; } }
+  if (int rcp = gs_reserve_partial(g, B)) return rcp;
   double *dc = centre, *drx = rad_x, *dru = rad_u;
   if (mem == TZ_MEM_HOST) {
     TZ_HIP(g->o_c.alloc((size_t)B * g->nseg * n)); TZ_HIP(g->o_rx.alloc((size_t)B * g->nseg * n)); TZ_HIP(g->o_ru.alloc((size_t)B * g->nseg * m));
@@ -700,7 +574,7 @@ int tube_stack_theta(tz_problem* p, int B, const double* d_e0, hipStream_t st) {
     TZ_HIP(p->ts_c.alloc((size_t)B * g->nseg * n)); TZ_HIP(p->ts_rx.alloc((size_t)B * g->nseg * n)); TZ_HIP(p->ts_ru.alloc((size_t)B * g->nseg * m));
     p->ts_cap = B;
   }
-  { const size_t need = (size_t)std::max(g->nchunk, 1) * (B <= 64 ? TZ_GS_NARROW_SUB : 1) * B * pq; if (need > g->pcap) { TZ_HIP(g->partial.alloc(need)); g->pcap = need; } }
+  if (int rcp = gs_reserve_partial(g, B)) return rcp;
   int rc = gs_eval(g, B, d_e0, p->ts_zeta.p, p->ts_c.p, p->ts_rx.p, p->ts_ru.p, st);
   if (rc) return rc;
   ThetaStackParams q{B, n, m, p->N, g->nseg, p->ntheta, p->ts_c.p, p->ts_rx.p, p->ts_ru.p, p->theta.p};
@@ -744,25 +618,10 @@ int tz_genstack_values(tz_genstack* g, int32_t seg, int32_t B, const double* e0,
 
 int tz_problem_create(int device, const tz_problem_desc* d, tz_problem** out) {
   if (!d || !out) TZ_FAIL(TZ_ERR_INVALID, "null argument");
-  if (d->abi_version != TZ_ABI_VERSION) TZ_FAIL(TZ_ERR_INVALID, "abi_version %d != %d", d->abi_version, TZ_ABI_VERSION);
-  if (d->pmax > TZ_PMAX) TZ_FAIL(TZ_ERR_UNSUPPORTED, "pmax=%d > %d powers of M_K not supported by tz_tube_kernel", d->pmax, TZ_PMAX);
-  if (d->n < 1 || d->n > TZ_NMAX || d->m < 1 || d->m > TZ_MMAX) TZ_FAIL(TZ_ERR_UNSUPPORTED, "dim_x must be 1..%d and dim_u 1..%d", TZ_NMAX, TZ_MMAX);
-  if (d->N < 1 || d->nz < d->N * d->m || d->mi < 1) TZ_FAIL(TZ_ERR_INVALID, "inconsistent sizes N=%d nz=%d mi=%d", d->N, d->nz, d->mi);
-  if (d->nz > 256) TZ_FAIL(TZ_ERR_UNSUPPORTED, "nz=%d > 256 decision variables not supported by tz_ipm_kernel", d->nz);
-  if (d->mi > 6 * TZ_THREADS) TZ_FAIL(TZ_ERR_UNSUPPORTED, "mi=%d > %d inequality rows not supported by tz_ipm_kernel", d->mi, 6 * TZ_THREADS);
-  if (d->ntheta != 2 * d->n + d->N * (2 * d->n + d->m)) TZ_FAIL(TZ_ERR_INVALID, "ntheta mismatch");
-  if (d->q.rows != d->nz || d->h.rows != d->mi) TZ_FAIL(TZ_ERR_INVALID, "affine map row counts do not match nz / mi");
-  for (int k = 0; k < d->N; ++k)
-    if (d->power[k] < 0 || d->power[k] > d->pmax) TZ_FAIL(TZ_ERR_INVALID, "power[%d]=%d outside 0..pmax", k, d->power[k]);
-  for (int r = 0; r < d->mi; ++r)
-    if (d->row_of[r] < 0 || d->row_of[r] >= std::max(d->nc_rows, 1)) TZ_FAIL(TZ_ERR_INVALID, "row_of[%d] out of range", r);
-  const int32_t known_flags = TZ_PLAN_UNFUSED | TZ_PLAN_ITEM_GRAM | TZ_PLAN_NO_STAIRCASE;
-  if (d->plan_flags & ~known_flags) TZ_FAIL(TZ_ERR_INVALID, "plan_flags 0x%x: unknown bits 0x%x", (unsigned)d->plan_flags, (unsigned)(d->plan_flags & ~known_flags));
-  int ndev = 0;
-  TZ_HIP(hipGetDeviceCount(&ndev));
-  if (ndev <= 0) TZ_FAIL(TZ_ERR_HIP, "no HIP device visible: the TZDDPC hot path has no CPU fallback");
-  if (device < 0 || device >= ndev) TZ_FAIL(TZ_ERR_INVALID, "device %d out of range (0..%d)", device, ndev - 1);
-  TZ_HIP(hipSetDevice(device));
+  int rc = tz_plan_check(*d, g_err);               // before the device query: a machine without a GPU reports a bad description as such
+  if (rc || (rc = use_device(device))) return rc;
+  TzPlan plan;
+  if ((rc = tz_plan_build(*d, plan, g_err))) return rc;
 
   tz_problem* p = new tz_problem();
   std::unique_ptr<tz_problem> guard(p);
@@ -773,306 +632,34 @@ int tz_problem_create(int device, const tz_problem_desc* d, tz_problem** out) {
   p->tol = d->tol > 0 ? d->tol : 1e-10; p->reg = d->reg > 0 ? d->reg : 1e-12;
   p->step_frac = (d->step_frac > 0 && d->step_frac < 1) ? d->step_frac : 0.99;
   p->cost_scale = d->cost_scale; p->r0 = d->r0;
-  const int nz = d->nz, mi = d->mi;
-  p->Tz = (nz + 3) / 4; p->nzp = 4 * p->Tz;
-  p->Kc = (mi + 3) / 4; p->mip = 4 * p->Kc;
-  const int Tz = p->Tz, Kc = p->Kc, nzp = p->nzp, mip = p->mip;
-  p->nquads = 0;
-  for (int I = 0; I < Tz; ++I) p->nquads += (I >> 2) + 1;
+  p->pl = plan;
+  p->fuse_enabled = plan.fused; p->have_shift = !plan.shift_var.empty();
+  p->ipm_fn = ipm_kernel_for(plan.maxr, plan.ncg, plan.wgs_per_cu, plan.tt);
+  if (!p->ipm_fn) TZ_FAIL(TZ_ERR_UNSUPPORTED, TZ_NO_VARIANT);
 
-  p->maxr = (mi + TZ_THREADS - 1) / TZ_THREADS; p->ncg = (nzp + 63) / 64;
-  p->tt = (p->ncg >= 2 || p->maxr > 4);
-  // Staircase ordering (tile-triangle class): the library keeps the variables in time order (v_k next to the epigraph variables
-  // of step k) and the rows by their last non-zero column, so that the non-zeros of G lie under a staircase: super-step s (16
-  // rows) touches only the tile columns 0 .. cmax[s], non-decreasing in s.  A unit of the blocked Gram is then active on a
-  // contiguous range of super-steps [s0, S) and runs there without a single mask test.  Purely structural: the time of v[k, j]
-  // (the first N m variables, reference tzddpc/tzddpc.py:155) is k, the time of any other variable the smallest, over the rows
-  // it appears in, of the latest input in that row.  Callers never see the ordering (outputs go through vpos / row_of).
-  std::vector<int> permc((size_t)nz), permr((size_t)mi), invc((size_t)nz), invr((size_t)mi);
-  std::iota(permc.begin(), permc.end(), 0); std::iota(permr.begin(), permr.end(), 0);
-  const int nv = d->N * d->m;
-  if (p->tt && !(d->plan_flags & TZ_PLAN_NO_STAIRCASE)) {
-    std::vector<int> rowt((size_t)mi, -1), colt((size_t)nz, 1 << 30);
-    for (int r = 0; r < mi; ++r) for (int c = 0; c < nv; ++c) if (d->G[(size_t)r * nz + c] != 0.0) rowt[r] = std::max(rowt[r], c / d->m);
-    for (int c = 0; c < nv; ++c) colt[c] = c / d->m;
-    for (int c = nv; c < nz; ++c) { for (int r = 0; r < mi; ++r) if (d->G[(size_t)r * nz + c] != 0.0) colt[c] = std::min(colt[c], rowt[r]); if (colt[c] == (1 << 30)) colt[c] = d->N; }
-    std::stable_sort(permc.begin(), permc.end(), [&](int a, int b) { return colt[a] < colt[b]; });
-    for (int i = 0; i < nz; ++i) invc[permc[i]] = i;
-    std::vector<int> last((size_t)mi, -1);
-    for (int r = 0; r < mi; ++r) for (int c = 0; c < nz; ++c) if (d->G[(size_t)r * nz + c] != 0.0) last[r] = std::max(last[r], invc[c]);
-    std::stable_sort(permr.begin(), permr.end(), [&](int a, int b) { return last[a] < last[b]; });
-    p->permc = permc; p->permr = permr; p->staircase = true;
-    std::vector<int> vp((size_t)nv);
-    for (int c = 0; c < nv; ++c) vp[c] = invc[c];
-    TZ_HIP(p->vpos.upload(vp));
-  }
-  for (int i = 0; i < nz; ++i) invc[permc[i]] = i;
-  for (int i = 0; i < mi; ++i) invr[permr[i]] = i;
-  // padded dense copies (device order)
-  std::vector<double> P((size_t)nzp * nzp, 0.0), G((size_t)mip * nzp, 0.0), Gp((size_t)(Kc + 1) * (Tz + 1) * 16, 0.0);   // tile Tz of every row and the last patch row stay zero (masked operands / prefetch padding)
-  for (int r = 0; r < nz; ++r) for (int c = 0; c < nz; ++c) P[(size_t)r * nzp + c] = d->P[(size_t)permc[r] * nz + permc[c]];
-  for (int r = 0; r < mi; ++r) for (int c = 0; c < nz; ++c) {
-    double v = d->G[(size_t)permr[r] * nz + permc[c]];
-    G[(size_t)r * nzp + c] = v;
-    Gp[((size_t)(r >> 2) * (Tz + 1) + (c >> 2)) * 16 + 4 * (r & 3) + (c & 3)] = v;
-  }
-  p->nP = 0;
-  for (int r = 0; r < nz; ++r) for (int c = 0; c < nz; ++c) if (P[(size_t)r * nzp + c] != 0.0) p->nP = r + 1;
-  // Gram plan: item = (block of 4 tile rows I0..I0+3, quads q0..q0+nq-1), k-list = chunks where the 16 columns are non-zero
-  std::vector<int> klist;
-  std::vector<IpmItem> items;
-  std::vector<double> cost;
-  const int NB = (Tz + 3) / 4;
-  for (int IB = 0; IB < NB; ++IB) {
-    const int kptr = (int)klist.size();
-    for (int kc = 0; kc < Kc; ++kc) {
-      bool nzr = false;
-      for (int r = 4 * kc; r < std::min(4 * kc + 4, mi) && !nzr; ++r)
-        for (int c = 16 * IB; c < std::min(16 * IB + 16, nz); ++c)
-          if (G[(size_t)r * nzp + c] != 0.0) { nzr = true; break; }
-      if (nzr) klist.push_back(kc);
-    }
-    const int klen = (int)klist.size() - kptr;
-    for (int z = 0; z < 8; ++z) klist.push_back(Kc);     // prefetch padding: the all-zero patch row
-    const int Ilast = std::min(4 * IB + 3, Tz - 1);
-    const int qmax = Ilast >> 2;          // quads 0..qmax exist for the last row of the block
-    for (int q0 = 0; q0 <= qmax; q0 += 2) {
-      IpmItem it{4 * IB, q0, std::min(2, qmax - q0 + 1), kptr, klen};
-      items.push_back(it);
-      cost.push_back((double)klen * 4 * it.nq + 8);
-    }
-  }
-  // LPT assignment to the 4 waves
-  std::vector<int> order(items.size());
-  std::iota(order.begin(), order.end(), 0);
-  std::sort(order.begin(), order.end(), [&](int a, int b) { return cost[a] > cost[b]; });
-  std::vector<std::vector<int>> per_wave(TZ_NWAVES);
-  double load[TZ_NWAVES] = {0, 0, 0, 0};
-  for (int idx : order) {
-    int w = (int)(std::min_element(load, load + TZ_NWAVES) - load);
-    per_wave[w].push_back(idx); load[w] += cost[idx];
-  }
-  std::vector<IpmItem> items_sorted;
-  std::vector<int> item_ptr(TZ_NWAVES + 1, 0);
-  p->mfma_gram = 0;
-  for (int w = 0; w < TZ_NWAVES; ++w) {
-    for (int idx : per_wave[w]) {
-      const IpmItem& it = items[idx];
-      items_sorted.push_back(it);
-      const int validI = std::min(4, Tz - it.I0);
-      p->mfma_gram += (int64_t)it.klen * validI * it.nq;
-      p->mfma_issued += (int64_t)it.klen * 8;
-    }
-    item_ptr[w + 1] = (int)items_sorted.size();
-  }
-  p->mfma_chol = 0;
-  for (int pp = 0; pp < Tz; ++pp)
-    for (int I = pp + 1; I < Tz; ++I) p->mfma_chol += (I >> 2) - ((pp + 1) >> 2) + 1;
-  p->mfma_issued += p->mfma_chol;
-
-  TZ_HIP(p->P.upload(P)); TZ_HIP(p->Gp.upload(Gp));
-  {
-    const int S = (Kc + 3) / 4;
-    std::vector<int> sm((size_t)S + 1, 0);
-    if (Tz <= 31) for (int r = 0; r < mi; ++r) for (int c = 0; c < nz; ++c) if (G[(size_t)r * nzp + c] != 0.0) sm[r >> 4] |= 1 << (c >> 2);
-    TZ_HIP(p->smask.upload(sm));
-  }
-  {
-    std::vector<std::vector<std::pair<int, double>>> byrow((size_t)mi), bycol((size_t)nz);
-    for (int r = 0; r < mi; ++r) for (int c = 0; c < nz; ++c) {
-      const double v = G[(size_t)r * nzp + c];
-      if (v != 0.0) { byrow[r].push_back({c, v}); bycol[c].push_back({r, v}); }
-    }
-    // G x: twice as many virtual lanes as rows, so the long rows can be cut up;  G'v: the 192 lanes of waves 1-3 per pass
-    TZ_HIP(p->eg.build(byrow, TZ_THREADS, 2 * mi, p->tt));
-    TZ_HIP(p->et.build(bycol, TZ_THREADS - 64, std::max(TZ_THREADS - 64, 2 * nz), p->tt));
-    p->nell = std::max(p->eg.VL, p->et.VL);
-  }
-  if (klist.empty()) klist.push_back(0);
-  p->nklist = std::max((int)klist.size(), (Kc + 3) / 4 + 1);     // the LDS k-list area doubles as the super-step mask table (ksplit)
-  TZ_HIP(p->klist.upload(klist)); TZ_HIP(p->items.upload(items_sorted)); TZ_HIP(p->item_ptr.upload(item_ptr));
-  TZ_HIP(p->q.upload(d->q, permc.data())); TZ_HIP(p->h.upload(d->h, permr.data())); TZ_HIP(p->par.upload(d->par));
+  const size_t n = d->n, m = d->m, N = d->N;
+  TZ_HIP(p->vpos.upload(plan.vpos));
+  TZ_HIP(p->P.upload(plan.P)); TZ_HIP(p->Gp.upload(plan.Gp)); TZ_HIP(p->smask.upload(plan.smask));
+  TZ_HIP(p->eg.upload(plan.eg)); TZ_HIP(p->et.upload(plan.et));
+  TZ_HIP(p->klist.upload(plan.klist)); TZ_HIP(p->items.upload(plan.items)); TZ_HIP(p->item_ptr.upload(plan.item_ptr));
+  TZ_HIP(p->q.upload(plan.q)); TZ_HIP(p->h.upload(plan.h)); TZ_HIP(p->par.upload(plan.par));
   TZ_HIP(p->par_lo.upload(d->par_lo, (size_t)p->npar)); TZ_HIP(p->par_hi.upload(d->par_hi, (size_t)p->npar));
-  TZ_HIP(p->Dz.upload(d->Dz, (size_t)nz));
-  if (d->rec_y || d->rec_c0 || d->rec_x0) {                              // equality-eliminated problem: affine recovery of v
-    if (!(d->rec_y && d->rec_c0 && d->rec_x0)) TZ_FAIL(TZ_ERR_INVALID, "rec_c0, rec_x0 and rec_y go together");
-    std::vector<double> ry((size_t)nv * nz);
-    for (int c = 0; c < nv; ++c) for (int k = 0; k < nz; ++k) ry[(size_t)c * nz + k] = d->rec_y[(size_t)c * nz + permc[k]];
-    TZ_HIP(p->recy.upload(ry)); TZ_HIP(p->rec0.upload(d->rec_c0, (size_t)nv)); TZ_HIP(p->recx.upload(d->rec_x0, (size_t)nv * d->n));
-  }
-  {                                                                      // xbar[1] = Phi_1 xbar0 + Gam_1 v with Gam_1 confined to v[0] (it is A xbar0 + B v[0], reference :166-170)
-    bool only_v0 = !(d->rec_y || d->rec_c0 || d->rec_x0);
-    for (int i = 0; i < d->n && only_v0; ++i) for (int c = d->m; c < nv; ++c) if (d->Gam[((size_t)d->n + i) * nv + c] != 0.0) { only_v0 = false; break; }
-    p->lean_epilogue = only_v0;
-  }
-  TZ_HIP(p->Phi.upload(d->Phi, (size_t)(d->N + 1) * d->n * d->n));
-  TZ_HIP(p->Gam.upload(d->Gam, (size_t)(d->N + 1) * d->n * d->N * d->m));
-  TZ_HIP(p->r1.upload(d->r1, (size_t)d->n)); TZ_HIP(p->R2.upload(d->R2, (size_t)d->n * d->n));
-  TZ_HIP(p->CK.upload(d->CK, (size_t)d->n * d->n)); TZ_HIP(p->DK.upload(d->DK, (size_t)d->n * d->n));
-  TZ_HIP(p->K.upload(d->K, (size_t)d->m * d->n));
-  {
-    // Resolvent of the tube recursion (tz_kernels.hip.h, TubeParams): with X_j = |C_K^j|, U_j = |K C_K^j|,
-    //   R_0 = D_K, R_d = D_K Tx_{d-1};  Tx_d = sum_{j<=d} X_{d-j} R_j;  Tu_d = sum_{j<=d} U_{d-j} R_j;  and C_K^l.
-    const int n = d->n, m = d->m, pm = d->pmax, nm = n + m;
-    std::vector<double> ckp((size_t)(pm + 1) * n * n, 0.0), T((size_t)std::max(pm, 1) * nm * n, 0.0), R((size_t)std::max(pm, 1) * n * n, 0.0);
-    for (int i = 0; i < n; ++i) ckp[(size_t)i * n + i] = 1.0;
-    for (int l = 1; l <= pm; ++l)
-      for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) {
-        double a = 0.0;
-        for (int k = 0; k < n; ++k) a += d->CK[i * n + k] * ckp[((size_t)(l - 1) * n + k) * n + j];
-        ckp[((size_t)l * n + i) * n + j] = a;
-      }
-    for (int dd = 0; dd < pm; ++dd) {
-      double* Rd = &R[(size_t)dd * n * n];
-      if (dd == 0) for (int e = 0; e < n * n; ++e) Rd[e] = d->DK[e];
-      else {
-        const double* Tp = &T[(size_t)(dd - 1) * nm * n];      // Tx_{d-1} = first n rows
-        for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) {
-          double a = 0.0;
-          for (int k = 0; k < n; ++k) a += d->DK[i * n + k] * Tp[k * n + j];
-          Rd[i * n + j] = a;
-        }
-      }
-      double* Td = &T[(size_t)dd * nm * n];
-      for (int jj = 0; jj <= dd; ++jj) {
-        const double* X = d->absCKpow + (size_t)(dd - jj) * n * n;
-        const double* U = d->absKCKpow + (size_t)(dd - jj) * m * n;
-        const double* Rj = &R[(size_t)jj * n * n];
-        for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) {
-          double a = 0.0;
-          for (int k = 0; k < n; ++k) a += X[i * n + k] * Rj[k * n + j];
-          Td[i * n + j] += a;
-        }
-        for (int i = 0; i < m; ++i) for (int j = 0; j < n; ++j) {
-          double a = 0.0;
-          for (int k = 0; k < n; ++k) a += U[i * n + k] * Rj[k * n + j];
-          Td[(n + i) * n + j] += a;
-        }
-      }
-    }
-    TZ_HIP(p->CKpow.upload(ckp.data(), ckp.size()));
-    TZ_HIP(p->Ttube.upload(T.data(), T.size()));
-  }
-  TZ_HIP(p->power.upload(d->power, (size_t)d->N));
-  {
-    std::vector<int> ro((size_t)mi); std::vector<double> as((size_t)mi);
-    for (int i = 0; i < mi; ++i) { ro[i] = d->row_of[permr[i]]; as[i] = d->act_scale[permr[i]]; }
-    TZ_HIP(p->row_of.upload(ro)); TZ_HIP(p->act_scale.upload(as));
-  }
-  if (d->shift_var && d->shift_row && d->shift_xscale && d->shift_lscale) {
-    for (int c = 0; c < nz; ++c) if (d->shift_var[c] < 0 || d->shift_var[c] >= nz) TZ_FAIL(TZ_ERR_INVALID, "shift_var[%d] out of range", c);
-    for (int r = 0; r < mi; ++r) if (d->shift_row[r] < 0 || d->shift_row[r] >= mi) TZ_FAIL(TZ_ERR_INVALID, "shift_row[%d] out of range", r);
-    std::vector<int> sv((size_t)nz), sr((size_t)mi); std::vector<double> xs((size_t)nz), ls((size_t)mi);
-    for (int i = 0; i < nz; ++i) { sv[i] = invc[d->shift_var[permc[i]]]; xs[i] = d->shift_xscale[permc[i]]; }
-    for (int i = 0; i < mi; ++i) { sr[i] = invr[d->shift_row[permr[i]]]; ls[i] = d->shift_lscale[permr[i]]; }
-    TZ_HIP(p->shift_var.upload(sv)); TZ_HIP(p->shift_row.upload(sr));
-    TZ_HIP(p->shift_xs.upload(xs)); TZ_HIP(p->shift_ls.upload(ls));
-    p->have_shift = true;
-  }
+  TZ_HIP(p->Dz.upload(d->Dz, (size_t)d->nz));
+  TZ_HIP(p->recy.upload(plan.recy)); TZ_HIP(p->rec0.upload(plan.rec0)); TZ_HIP(p->recx.upload(plan.recx));
+  TZ_HIP(p->Phi.upload(d->Phi, (N + 1) * n * n));
+  TZ_HIP(p->Gam.upload(d->Gam, (N + 1) * n * N * m));
+  TZ_HIP(p->r1.upload(d->r1, n)); TZ_HIP(p->R2.upload(d->R2, n * n));
+  TZ_HIP(p->CK.upload(d->CK, n * n)); TZ_HIP(p->DK.upload(d->DK, n * n));
+  TZ_HIP(p->K.upload(d->K, m * n));
+  TZ_HIP(p->CKpow.upload(plan.CKpow)); TZ_HIP(p->Ttube.upload(plan.Ttube));
+  TZ_HIP(p->power.upload(d->power, N));
+  TZ_HIP(p->row_of.upload(plan.row_of)); TZ_HIP(p->act_scale.upload(plan.act_scale));
+  TZ_HIP(p->shift_var.upload(plan.shift_var)); TZ_HIP(p->shift_row.upload(plan.shift_row));
+  TZ_HIP(p->shift_xs.upload(plan.shift_xs)); TZ_HIP(p->shift_ls.upload(plan.shift_ls));
+  TZ_HIP(p->gunits.upload(plan.gunits)); TZ_HIP(p->gunit_ptr.upload(plan.gunit_ptr));
+  p->permc = std::move(plan.permc); p->permr = std::move(plan.permr);      // tz_debug_fetch; the other host tables end here
 
-  p->ntube = (d->pmax + 1) * d->n * d->n + std::max(d->pmax, 1) * (d->n + d->m) * d->n         // tube tables
-             + 3 * d->n * d->n + 2 * d->n * d->m + d->n + d->n * d->N * d->m + d->N * d->m        // recovery / plant constants
-             + (d->N + 1) / 2;                                                                    // power[k] (ints)
-  const size_t LDS_MAX = 160 * 1024;
-  auto fail_lds = [&](size_t need) { char b[256]; snprintf(b, sizeof(b), "not supported: the problem needs %zu bytes of LDS per workgroup (nz=%d, mi=%d); limit is 160 KiB", need, nz, mi); g_err = b; return TZ_ERR_UNSUPPORTED; };
-  int wgs_per_cu = 1;
-  if (p->tt) {
-    // ---- tile-triangle class: masks and work plan of the blocked Gram, tile stride, workgroups per CU ----------------------
-    p->ksplit = false;
-    p->ntile = Tz * (Tz + 1) / 2;
-    const int S = (Kc + 3) / 4;
-    // staircase: last non-zero tile column of every super-step, made non-decreasing (it is, when the ordering above is on);
-    // sfirst[I] = first super-step that touches tile column I
-    std::vector<int> cmaxs((size_t)S, -1);
-    for (int r = 0; r < mi; ++r) for (int c = 0; c < nz; ++c) if (G[(size_t)r * nzp + c] != 0.0) cmaxs[r >> 4] = std::max(cmaxs[r >> 4], c >> 2);
-    std::vector<int> sfirst((size_t)Tz + 1, S);
-    for (int sIdx = S - 1; sIdx >= 0; --sIdx) for (int I = 0; I <= cmaxs[sIdx]; ++I) sfirst[I] = sIdx;
-    // units: the tile index range is cut into near-equal ranges of at most TZ_GU tiles; a unit is a pair of ranges (row range >=
-    // column range).  Cost = MFMAs it issues (masked); LPT over the waves; the range size with the smallest makespan wins.
-    // units: the tile index range (padded with all-zero tile columns up to a multiple of U) is cut into ranges of exactly U tiles;
-    // a unit is a pair of ranges (row range >= column range).  Cost = MFMAs + loads it issues; LPT over the waves; the U in
-    // [UMAX - 2, UMAX] with the smallest makespan wins.
-    std::vector<TzGUnit> best_units; std::vector<int> best_ptr; double best_span = 1e300; int best_u = 0;
-    auto plan = [&](int UMAX) {
-    best_units.clear(); best_span = 1e300;
-    for (int U = std::max(1, UMAX - 2); U <= UMAX; ++U) {
-      const int nrange = (Tz + U - 1) / U;
-      std::vector<TzGUnit> units; std::vector<double> cost;
-      for (int a = 0; a < nrange; ++a) for (int b = 0; b <= a; ++b) {
-        TzGUnit u{a * U, b * U, sfirst[a * U]};
-        const double per = (a == b) ? 0.5 * U * (U + 1) + 0.4 * U : (double)U * U + 0.4 * 2 * U;   // MFMAs + loads of one super-step
-        units.push_back(u); cost.push_back(per * (S - u.s0 + 3) + 60.0);   // + pipeline fill, fold / store
-      }
-      std::vector<int> order(units.size());
-      std::iota(order.begin(), order.end(), 0);
-      std::sort(order.begin(), order.end(), [&](int x, int y) { return cost[x] > cost[y]; });
-      std::vector<std::vector<int>> per_wave(TZ_NWAVES); double load[TZ_NWAVES] = {0, 0, 0, 0};
-      for (int idx : order) { int w = (int)(std::min_element(load, load + TZ_NWAVES) - load); per_wave[w].push_back(idx); load[w] += cost[idx]; }
-      const double span = *std::max_element(load, load + TZ_NWAVES);
-      if (span < best_span) {
-        best_span = span; best_u = U; best_units.clear(); best_ptr.assign(TZ_NWAVES + 1, 0);
-        for (int w = 0; w < TZ_NWAVES; ++w) { for (int idx : per_wave[w]) best_units.push_back(units[idx]); best_ptr[w + 1] = (int)best_units.size(); }
-      }
-    }
-    };
-    p->nklist = 2;
-    // LDS: two workgroups per CU with the padded tile stride if that fits, else one; the partial-sum buffer of the G x product
-    // shrinks from two virtual lanes per row to one before the tile stride loses its padding
-    auto lds_for = [&](int TS, int nell) { return tz_ipm_lds_doubles((size_t)p->ntile * TS, 1, Tz, nzp, mip, p->nklist, p->ntheta, 0, p->ntube, nell) * sizeof(double); };
-    const int nell_full = p->nell;
-    DevEll eg_small; int nell_small = nell_full;
-    bool small_built = false;
-    auto need_small = [&]() -> hipError_t {
-      if (small_built) return hipSuccess;
-      std::vector<std::vector<std::pair<int, double>>> byrow((size_t)mi);
-      for (int r = 0; r < mi; ++r) for (int c = 0; c < nz; ++c) { const double v = G[(size_t)r * nzp + c]; if (v != 0.0) byrow[r].push_back({c, v}); }
-      hipError_t e = eg_small.build(byrow, TZ_THREADS, mi, p->tt);
-      nell_small = std::max(eg_small.VL, p->et.VL); small_built = true;
-      return e;
-    };
-    struct Cand { int TS; bool small; int wgs; };
-    const Cand cands[] = {{17, false, 2}, {17, true, 2}, {17, false, 1}, {17, true, 1}, {16, true, 1}};
-    bool placed = false;
-    for (const Cand& c : cands) {
-      if (c.small) TZ_HIP(need_small());
-      const size_t need = lds_for(c.TS, c.small ? nell_small : nell_full);
-      if (need * c.wgs <= LDS_MAX) {
-        p->TS = c.TS; wgs_per_cu = c.wgs; p->lds_bytes = need;
-        if (c.small) { p->eg.swap(eg_small); p->nell = nell_small; }
-        placed = true; break;
-      }
-    }
-    if (!placed) { TZ_HIP(need_small()); return fail_lds(lds_for(16, nell_small)); }
-    p->hsize = (size_t)p->ntile * p->TS;
-    bool ttk = false;
-    p->ipm_fn = ipm_kernel_for(p->maxr, p->ncg, wgs_per_cu, ttk);
-    if (p->maxr > 4) wgs_per_cu = 1;                                   // those variants exist for one workgroup per CU only
-    plan(TZ_TT_GU(wgs_per_cu));                                        // unit size <= what the chosen variant's register budget holds
-    if (best_units.empty()) TZ_FAIL(TZ_ERR_UNSUPPORTED, "no Gram plan for Tz=%d", Tz);
-    p->gu = best_u;
-    TZ_HIP(p->gunits.upload(best_units)); TZ_HIP(p->gunit_ptr.upload(best_ptr));
-    p->mfma_gram = (int64_t)best_span; p->mfma_chol = (int64_t)Tz * Tz * Tz / 24; p->mfma_issued = p->mfma_gram * TZ_NWAVES + p->mfma_chol;
-  } else {
-    p->ksplit = (p->Tz <= TZ_KS_TZ) && !(d->plan_flags & TZ_PLAN_ITEM_GRAM);
-    p->hsize = (size_t)p->nquads * TZ_QSTR;
-    // nz <= 64: the 128-register variant, h and G x of the rows parked in LDS
-    p->lds_bytes = tz_ipm_lds_doubles(p->hsize, 0, Tz, nzp, mip, p->nklist, p->ntheta, p->ksplit ? 1 : 0, p->ntube, p->nell, 1) * sizeof(double);
-    if (p->lds_bytes > LDS_MAX) return fail_lds(p->lds_bytes);
-    wgs_per_cu = (int)(LDS_MAX / std::max<size_t>(p->lds_bytes, 1));
-    bool ttk = false;
-    p->ipm_fn = ipm_kernel_for(p->maxr, p->ncg, wgs_per_cu, ttk);
-  }
-  if (!p->ipm_fn) TZ_FAIL(TZ_ERR_UNSUPPORTED, "this development build (TZ_ONLY_SMALL) carries only the mi <= 256, nz <= 64 kernel");
-  {                                                                     // the G x / G'v tables were built for the class decided above
-    bool ttk = false;
-    (void)ipm_kernel_for(p->maxr, p->ncg, wgs_per_cu, ttk);
-    if (ttk != p->tt) TZ_FAIL(TZ_ERR_UNSUPPORTED, "kernel class and table format disagree (development build?)");
-  }
-  TZ_HIP(hipFuncSetAttribute((const void*)p->ipm_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds_bytes));
-  if (d->plan_flags & TZ_PLAN_UNFUSED) p->fuse_enabled = false;
-  // the tube pass of the fused step keeps |C_K^l e0| (pmax n doubles) in the factor storage, which is free at that point: a short-horizon,
-  // large-n problem whose factor is smaller than that runs the four-kernel step instead (tz_tube_kernel has its own scratch)
-  if ((size_t)std::max(p->pmax, 1) * p->n > p->hsize) p->fuse_enabled = false;
+  TZ_HIP(hipFuncSetAttribute((const void*)p->ipm_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->pl.lds_bytes));
   if (p->prof) { TZ_HIP(p->prof_buf.alloc(PH_COUNT + 16)); TZ_HIP(hipMemset(p->prof_buf.p, 0, (PH_COUNT + 16) * sizeof(unsigned long long))); }
   TZ_HIP(p->work_buf.alloc(3));
   TZ_HIP(hipMemset(p->work_buf.p, 0, 3 * sizeof(unsigned long long)));
@@ -1373,10 +960,10 @@ int tz_ipm_work_get(tz_problem* p, int64_t* factorizations, int64_t* trajectory_
 int tz_ipm_plan_info(tz_problem* p, int64_t* mfma_gram_per_iter, int64_t* mfma_chol_per_iter, int64_t* mfma_issued_per_iter,
                      int64_t* lds_bytes, int64_t* patch_bytes) {
   if (!p) TZ_FAIL(TZ_ERR_INVALID, "null problem");
-  if (mfma_gram_per_iter) *mfma_gram_per_iter = p->mfma_gram;
-  if (mfma_chol_per_iter) *mfma_chol_per_iter = p->mfma_chol;
-  if (mfma_issued_per_iter) *mfma_issued_per_iter = p->mfma_issued;
-  if (lds_bytes) *lds_bytes = (int64_t)p->lds_bytes;
+  if (mfma_gram_per_iter) *mfma_gram_per_iter = p->pl.mfma_gram;
+  if (mfma_chol_per_iter) *mfma_chol_per_iter = p->pl.mfma_chol;
+  if (mfma_issued_per_iter) *mfma_issued_per_iter = p->pl.mfma_issued;
+  if (lds_bytes) *lds_bytes = (int64_t)p->pl.lds_bytes;
   if (patch_bytes) *patch_bytes = (int64_t)p->Gp.n * 8;
   return TZ_OK;
 }
@@ -1384,8 +971,8 @@ int tz_ipm_plan_info(tz_problem* p, int64_t* mfma_gram_per_iter, int64_t* mfma_c
 int tz_problem_plan_get(tz_problem* p, int32_t* fused, int32_t* superstep_gram, int32_t* staircase) {
   if (!p) TZ_FAIL(TZ_ERR_INVALID, "null problem");
   if (fused) *fused = p->fuse_enabled ? 1 : 0;
-  if (superstep_gram) *superstep_gram = p->ksplit ? 1 : 0;
-  if (staircase) *staircase = p->staircase ? 1 : 0;
+  if (superstep_gram) *superstep_gram = p->pl.ksplit ? 1 : 0;
+  if (staircase) *staircase = p->pl.staircase ? 1 : 0;
   return TZ_OK;
 }
 

@@ -238,44 +238,53 @@ def _csr(M: np.ndarray, c0: np.ndarray, keep: list):
     return AffMap(rows, _ptr(ptr, _ip), _ptr(col, _ip), _ptr(val, _dp), _ptr(c0, _dp))
 
 
-class Problem:
-    """Owner of one ``tz_problem`` handle."""
-
-    def __init__(self, device: int, *, n, m, N, P, G, q0, Qt, h0, Ht, par0, Part, par_lo, par_hi, cost_scale, r0, r1, R2,
+def problem_desc(*, n, m, N, P, G, q0, Qt, h0, Ht, par0, Part, par_lo, par_hi, cost_scale, r0, r1, R2,
                  Dz, Phi, Gam, nc_rows, row_of, act_scale, CK, DK, K, pmax, absCKpow, absKCKpow, power,
                  max_iter=40, tol=1e-10, reg=1e-12, step_frac=0.99999,
                  shift_var=None, shift_row=None, shift_xscale=None, shift_lscale=None, rec_c0=None, rec_x0=None, rec_y=None, plan_flags=0):
+    """The ``tz_problem_desc`` of a problem -> (ProblemDesc, the numpy arrays it points into: keep them as long as the desc is used)."""
+    keep = []
+    d = ProblemDesc()
+    d.abi_version = TZ_ABI_VERSION
+    d.n, d.m, d.N = int(n), int(m), int(N)
+    P = _f64(P); G = _f64(G)
+    d.nz, d.mi = P.shape[0], G.shape[0]
+    d.ntheta = 2 * n + N * (2 * n + m)
+    arrs = dict(P=P, G=G, r1=_f64(r1), R2=_f64(R2), Dz=_f64(Dz), Phi=_f64(Phi), Gam=_f64(Gam), act_scale=_f64(act_scale), CK=_f64(CK), DK=_f64(DK),
+                K=_f64(K), absCKpow=_f64(absCKpow), absKCKpow=_f64(absKCKpow))
+    for k, a in arrs.items():
+        setattr(d, k, _ptr(a, _dp)); keep.append(a)
+    d.q = _csr(Qt, q0, keep); d.h = _csr(Ht, h0, keep); d.par = _csr(Part, par0, keep)
+    plo = _f64(par_lo) if len(par_lo) else np.zeros(1); phi = _f64(par_hi) if len(par_hi) else np.zeros(1)
+    keep += [plo, phi]
+    d.par_lo = _ptr(plo, _dp); d.par_hi = _ptr(phi, _dp)
+    d.cost_scale = float(cost_scale); d.r0 = float(r0)
+    ro = _i32(row_of); pw = _i32(power); keep += [ro, pw]
+    d.nc_rows = int(nc_rows); d.row_of = _ptr(ro, _ip)
+    d.pmax = int(pmax); d.power = _ptr(pw, _ip)
+    d.max_iter = int(max_iter); d.tol = float(tol); d.reg = float(reg); d.step_frac = float(step_frac)
+    d.plan_flags = int(plan_flags)
+    if shift_var is not None:
+        sv, sr, xs, ls = _i32(shift_var), _i32(shift_row), _f64(shift_xscale), _f64(shift_lscale)
+        keep += [sv, sr, xs, ls]
+        d.shift_var = _ptr(sv, _ip); d.shift_row = _ptr(sr, _ip); d.shift_xscale = _ptr(xs, _dp); d.shift_lscale = _ptr(ls, _dp)
+    if rec_y is not None:
+        rc, rx, ry = _f64(rec_c0).reshape(N * m), _f64(rec_x0).reshape(N * m, n), _f64(rec_y).reshape(N * m, d.nz)
+        keep += [rc, rx, ry]
+        d.rec_c0 = _ptr(rc, _dp); d.rec_x0 = _ptr(rx, _dp); d.rec_y = _ptr(ry, _dp)
+    return d, keep
+
+
+class Problem:
+    """Owner of one ``tz_problem`` handle."""
+
+    def __init__(self, device: int, **desc):
+        """`desc`: the keyword arguments of ``problem_desc``."""
         L = lib()
-        keep = []
-        d = ProblemDesc()
-        d.abi_version = TZ_ABI_VERSION
-        d.n, d.m, d.N = int(n), int(m), int(N)
-        P = _f64(P); G = _f64(G)
-        d.nz, d.mi = P.shape[0], G.shape[0]
-        d.ntheta = 2 * n + N * (2 * n + m)
-        arrs = dict(P=P, G=G, r1=_f64(r1), R2=_f64(R2), Dz=_f64(Dz), Phi=_f64(Phi), Gam=_f64(Gam), act_scale=_f64(act_scale), CK=_f64(CK), DK=_f64(DK),
-                    K=_f64(K), absCKpow=_f64(absCKpow), absKCKpow=_f64(absKCKpow))
-        for k, a in arrs.items():
-            setattr(d, k, _ptr(a, _dp)); keep.append(a)
-        d.q = _csr(Qt, q0, keep); d.h = _csr(Ht, h0, keep); d.par = _csr(Part, par0, keep)
-        plo = _f64(par_lo) if len(par_lo) else np.zeros(1); phi = _f64(par_hi) if len(par_hi) else np.zeros(1)
-        keep += [plo, phi]
-        d.par_lo = _ptr(plo, _dp); d.par_hi = _ptr(phi, _dp)
-        d.cost_scale = float(cost_scale); d.r0 = float(r0)
-        ro = _i32(row_of); pw = _i32(power); keep += [ro, pw]
-        d.nc_rows = int(nc_rows); d.row_of = _ptr(ro, _ip)
-        d.pmax = int(pmax); d.power = _ptr(pw, _ip)
-        d.max_iter = int(max_iter); d.tol = float(tol); d.reg = float(reg); d.step_frac = float(step_frac)
-        d.plan_flags = int(plan_flags)
-        if shift_var is not None:
-            sv, sr, xs, ls = _i32(shift_var), _i32(shift_row), _f64(shift_xscale), _f64(shift_lscale)
-            keep += [sv, sr, xs, ls]
-            d.shift_var = _ptr(sv, _ip); d.shift_row = _ptr(sr, _ip); d.shift_xscale = _ptr(xs, _dp); d.shift_lscale = _ptr(ls, _dp)
-        if rec_y is not None:
-            rc, rx, ry = _f64(rec_c0).reshape(N * m), _f64(rec_x0).reshape(N * m, n), _f64(rec_y).reshape(N * m, d.nz)
-            keep += [rc, rx, ry]
-            d.rec_c0 = _ptr(rc, _dp); d.rec_x0 = _ptr(rx, _dp); d.rec_y = _ptr(ry, _dp)
-        self.n, self.m, self.N, self.nz, self.mi, self.nc_rows, self.ntheta = int(n), int(m), int(N), d.nz, d.mi, int(nc_rows), d.ntheta
+        d, keep = problem_desc(**desc)
+        n, m, N, G, P = d.n, d.m, d.N, desc["G"], desc["P"]
+        Qt, Ht, Part = desc["Qt"], desc["Ht"], desc["Part"]
+        self.n, self.m, self.N, self.nz, self.mi, self.nc_rows, self.ntheta = d.n, d.m, d.N, d.nz, d.mi, d.nc_rows, d.ntheta
         # structure-aware algorithmic work of one interior-point factorisation + its two solves (what bench.py's roofline
         # counts): sparse outer products of the rows of G, Cholesky, four G / G' products, two triangular solve pairs, P x
         Gn = np.asarray(G).reshape(d.mi, d.nz); nnz_r = (Gn != 0).sum(axis=1).astype(np.float64)
@@ -420,7 +429,9 @@ class Problem:
 class GenStack:
     """Owner of one ``tz_genstack`` handle: the literal stacked-generator tubes of a problem on the device (kernel K1g)."""
 
-    def __init__(self, device: int, st):
+    @staticmethod
+    def desc(st):
+        """The ``tz_genstack_desc`` of a ``genstack.Stack`` -> (GenstackDesc, the numpy arrays it points into)."""
         d = GenstackDesc()
         keep = []
         d.n, d.m, d.N, d.nseg = int(st.n), int(st.m), int(st.N), int(st.nseg)
@@ -433,6 +444,10 @@ class GenStack:
             keep.append(a); setattr(d, name, _ptr(a, _dp))
         if np.any(st.cZ):
             a = _f64(st.cZ); keep.append(a); d.cZ = _ptr(a, _dp)
+        return d, keep
+
+    def __init__(self, device: int, st):
+        d, keep = self.desc(st)
         self.n, self.m, self.N, self.nseg = d.n, d.m, d.N, d.nseg
         self.num_generators = np.diff(np.asarray(st.seg_ptr)).astype(np.int64)
         h = C.c_void_p()

@@ -320,8 +320,14 @@ class TZDDPC(object):
         return self._native
 
     def _native_from_qp(self, qp_full, solver_kwargs):
-        """Two-sided parametric QP -> device problem (``tz_problem_create``): equality elimination, one-sided rows, Ruiz
-        equilibration, warm-start shift maps.  Returns (native.Problem, dict(elim, scal, row_of, qp))."""
+        """Two-sided parametric QP -> device problem (``tz_problem_create``).  Returns (native.Problem, dict(elim, scal, row_of, qp))."""
+        args, info = self._native_args(qp_full, solver_kwargs)
+        return native.Problem(self.device, **args), info
+
+    @staticmethod
+    def _native_args(qp_full, solver_kwargs):
+        """Two-sided parametric QP -> the description the device problem is created from: equality elimination, one-sided rows, Ruiz
+        equilibration, warm-start shift maps.  Returns (keyword arguments of native.problem_desc, dict(elim, scal, row_of, qp))."""
         n, m, horizon = qp_full.n, qp_full.m, qp_full.N
         qp = qp_full
         # `==` rows of build_constraints (reference :213-219) are eliminated here: the kernel sees inequality rows only and
@@ -356,8 +362,8 @@ class TZDDPC(object):
         opts = dict(max_iter=int(solver_kwargs.pop("max_iter", 40)), tol=float(solver_kwargs.pop("tol", 1e-10)),
                     reg=float(solver_kwargs.pop("reg", 1e-12)), step_frac=float(solver_kwargs.pop("step_frac", 0.99999)),
                     plan_flags=int(solver_kwargs.pop("plan_flags", 0)))
-        nat = native.Problem(
-            self.device, n=n, m=m, N=int(horizon),
+        args = dict(
+            n=n, m=m, N=int(horizon),
             P=c * D[:, None] * qp.P * D[None, :], G=E[:, None] * G * D[None, :],
             q0=c * D * qp.q0, Qt=(c * D)[:, None] * qp.Qt, h0=E * h0, Ht=E[:, None] * Ht,
             par0=qp.f0, Part=qp.Ft, par_lo=qp.pl, par_hi=qp.pu,
@@ -365,7 +371,7 @@ class TZDDPC(object):
             nc_rows=nc_rows, row_of=row_of, act_scale=c / (E * E), **rec,
             CK=qp.tube.CK, DK=qp.tube.DK, K=qp.tube.K, pmax=qp.tube.pmax,
             absCKpow=qp.tube.absCKpow, absKCKpow=qp.tube.absKCKpow, power=qp.tube.power, **shift, **opts)
-        return nat, dict(elim=elim, scal=(D, E, c), row_of=row_of, qp=qp)
+        return args, dict(elim=elim, scal=(D, E, c), row_of=row_of, qp=qp)
 
     def _calibration_noise(self, Bn, T, seed=12345):
         """Disturbances of the build-time calibration loops: uniformly random vertices of W (what the examples' plants draw,
