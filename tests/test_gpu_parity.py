@@ -352,6 +352,82 @@ def test_fused_step_equals_four_kernel_step(built):
         np.testing.assert_allclose(a["cost"], b["cost"], rtol=1e-9, atol=1e-9)
 
 
+@pytest.mark.parametrize("case", ["di_n20", "di_n40"])
+def test_three_entry_points_are_one_closed_loop(built, case):
+    """tz_mpc_step called T times, tz_mpc_run(T) and tz_simulate_batch(T) drive the same closed loop from the same start (centre of X0,
+    vertex disturbances, tz_problem_reset_warm before each): one runner behind the three entry points.
+
+    Four kernels per step (TZ_PLAN_UNFUSED): the three issue the same kernels on the same values -- everything they expose agrees bit
+    for bit.  Fused: the inner steps of tz_mpc_run take the lean epilogue, single-step launches and tz_simulate_batch the full one --
+    rounding differences against tz_mpc_run, bound REL (1 + max |value|) as for split launches above; tz_mpc_step against
+    tz_simulate_batch bit for bit.  Each pair is held to the strictest of the two that the commit before the runner met; its
+    largest gaps (64 trajectories, 8 steps; the runner leaves every figure as it was): unfused 0 everywhere; fused step/sim 0; fused
+    step/run and run/sim, di_n20: x 8.2e-13, xbar 8.6e-13, e 1.3e-13, u 8.8e-13; di_n40: x 2.4e-11, xbar 2.5e-11, e 3.8e-12, u 2.6e-11
+    (bound: 2e-6); status equal in every pair.
+
+    Launch counts (tz_timing_get) follow from the code: four kernels per step in every class on the unfused plan; one interior-point
+    launch per call and nothing else on the fused plan."""
+    import torch
+    from tzddpc_amd import native
+    from tzddpc_amd.dist import vertex_noise
+    Bn, T = 64, 8
+    # what the fused plan gave bit for bit before the runner: single-step launches against tz_simulate_batch (both take the full epilogue)
+    FUSED_BITWISE = {("step", "sim", "u"), ("step", "sim", "u_last"), ("step", "sim", "x")}
+    dev = torch.device("cuda", 0)
+    f64 = dict(dtype=torch.float64, device=dev)
+    for plan, flags in (("fused", 0), ("unfused", native.TZ_PLAN_UNFUSED)):
+        ctl, (A, B, zon) = common.gpu_controller(case, plan_flags=flags)
+        nat = ctl._native; n, m = ctl.qp.n, ctl.qp.m
+        assert nat.plan_info()["fused"] == (plan == "fused")
+        w_bt = torch.from_numpy(np.ascontiguousarray(vertex_noise(zon.W.compute_vertices(), 0, Bn, T))).to(dev)       # [trajectory, step]
+        w_tb = w_bt.transpose(0, 1).contiguous()                                                                        # [step, trajectory]
+        At = torch.from_numpy(np.ascontiguousarray(A, dtype=np.float64)).to(dev)
+        Bt = torch.from_numpy(np.ascontiguousarray(B, dtype=np.float64).reshape(n, m)).to(dev)
+        x0 = torch.from_numpy(np.tile(zon.X0.center, (Bn, 1))).to(dev)
+        torch.cuda.synchronize()
+        runs, counts = {}, {}
+        for way in ("step", "run", "sim"):
+            x = x0.clone(); xbar = x0.clone(); e = torch.zeros_like(x0)
+            u = torch.zeros((Bn, m), **f64); cost = torch.zeros(Bn, **f64); st = torch.zeros(Bn, dtype=torch.int32, device=dev)
+            xt = torch.zeros((Bn, T + 1, n), **f64); ut = torch.zeros((Bn, T, m), **f64); ct = torch.zeros((Bn, T), **f64)
+            torch.cuda.synchronize()
+            nat.reset_warm(); nat.timing_enable(True)
+            r = {}
+            if way == "step":
+                us, first = [], np.zeros(Bn, dtype=np.int32)
+                for t in range(T):
+                    nat.mpc_step_ptr(Bn, x.data_ptr(), xbar.data_ptr(), e.data_ptr(), w_tb[t].data_ptr(), At.data_ptr(), Bt.data_ptr(), u.data_ptr(), cost.data_ptr(), st.data_ptr())
+                    nat.sync()
+                    us.append(u.cpu().numpy().copy()); s = st.cpu().numpy()
+                    first = np.where(first != 0, first, s)                       # what the sticky record of the other two keeps
+                r = dict(x=x, xbar=xbar, e=e, u=np.stack(us, axis=1), u_last=us[-1], status=first)
+            elif way == "run":
+                nat.mpc_run_ptr(Bn, T, x.data_ptr(), xbar.data_ptr(), e.data_ptr(), w_tb.data_ptr(), At.data_ptr(), Bt.data_ptr(), u.data_ptr(), cost.data_ptr(), st.data_ptr())
+                nat.sync()
+                r = dict(x=x, xbar=xbar, e=e, u_last=u, status=st)
+            else:
+                nat.simulate_batch_ptr(Bn, T, x0.data_ptr(), w_bt.data_ptr(), At.data_ptr(), Bt.data_ptr(), xt.data_ptr(), ut.data_ptr(), ct.data_ptr(), st.data_ptr())
+                nat.sync()
+                r = dict(x=xt[:, T], u=ut, u_last=ut[:, T - 1], status=st)
+            counts[way] = [nat.timing_get(k)[1] for k in range(4)]                # tube + affine, interior point, finish, plant
+            nat.timing_enable(False)
+            runs[way] = {k: (v.cpu().numpy().copy() if torch.is_tensor(v) else np.asarray(v)) for k, v in r.items()}
+            assert (runs[way]["status"] == 0).all(), (plan, way, runs[way]["status"])
+        if plan == "fused":
+            assert counts == {"step": [0, T, 0, 0], "run": [0, 1, 0, 0], "sim": [0, 1, 0, 0]}, counts
+        else:
+            assert counts == {w: [T, T, T, T] for w in ("step", "run", "sim")}, counts
+        pairs = [(a, b, q) for a, b in (("step", "run"), ("step", "sim"), ("run", "sim")) for q in sorted(set(runs[a]) & set(runs[b]))]
+        for a, b, q in pairs:                                                     # every figure before the first assertion
+            print(f"entry-point gap {case} {plan} {a}/{b} {q}: {np.abs(runs[a][q] - runs[b][q]).max():.3e}")
+        for a, b, q in pairs:
+            ra, rb = runs[a][q], runs[b][q]
+            if plan == "unfused" or q == "status" or (a, b, q) in FUSED_BITWISE:
+                assert np.array_equal(ra, rb), (plan, a, b, q, np.abs(ra - rb).max())
+            else:
+                np.testing.assert_allclose(rb, ra, rtol=0, atol=REL * (1 + np.abs(ra).max()), err_msg=f"{plan} {a}/{b} {q}")
+
+
 def test_superstep_gram_equals_item_plan_gram(built):
     """nz <= 40 problems form the Gram by super-steps; plan_flags TZ_PLAN_ITEM_GRAM selects the item-plan Gram that larger problems
     use.  Same arithmetic, different order: closed loops agree to rounding.  di_n20_k1 (58 variables) takes the item plan either

@@ -102,6 +102,20 @@ def test_header_symbols_are_exported(built):
     assert L.tz_abi_version() == native.TZ_ABI_VERSION
 
 
+@pytest.mark.parametrize("libname", ["libtzddpc_hip.so", "libtzddpc_hip_prof.so"])
+def test_libraries_export_nothing_but_the_header(built, libname):
+    """The dynamic symbol table of both builds: every defined name that is not a mangled or reserved one (leading underscore) is an
+    entry point of include/tzddpc.h -- an internal helper or a kernel given C linkage by accident shows up here."""
+    import subprocess
+    from tzddpc_amd import native
+    path = os.path.join(os.path.dirname(native.__file__), "lib", libname)
+    out = subprocess.check_output(["nm", "-D", "--defined-only", path], text=True)
+    defined = {ln.split()[-1].split("@")[0] for ln in out.splitlines() if ln.strip()}
+    assert defined & set(native.EXPORTED_SYMBOLS) == set(native.EXPORTED_SYMBOLS)
+    stray = sorted(s for s in defined if not s.startswith("_") and s not in native.EXPORTED_SYMBOLS)
+    assert not stray, stray
+
+
 def test_plan_flags_of_header_and_binding_agree():
     from tzddpc_amd import native
     hdr = open(os.path.join(common.__file__.rsplit("/tests/", 1)[0], "include", "tzddpc.h")).read()

@@ -169,29 +169,32 @@ def check_plan(shim, args, flags, pl):
     assert pl["nell"] == max(pl["eg.VL"], pl["et.VL"])
 
     # ---- Gram item plan, super-step masks ------------------------------------------------------------------------------------------
-    klist, items, item_ptr = pl["klist"], pl["items"], pl["item_ptr"]
-    assert ((klist >= 0) & (klist <= Kc)).all()
-    nzpatch = Gpad.reshape(Kc + 1, 4, Tz + 1, 4).any(axis=(1, 3))             # [patch row, tile column]
-    quads = []
-    for it in items:
-        IB = it["I0"] // 4
-        assert it["I0"] % 4 == 0 and it["nq"] >= 1
-        lst = klist[it["kptr"]:it["kptr"] + it["klen"]]
-        want = np.nonzero(nzpatch[:Kc, 4 * IB:min(4 * IB + 4, Tz)].any(axis=1))[0]
-        assert np.array_equal(lst, want)                                       # in the list iff a non-zero in the block, all < Kc
-        assert (klist[it["kptr"] + it["klen"]:it["kptr"] + it["klen"] + 8] == Kc).all() and it["kptr"] + it["klen"] + 8 <= len(klist)
-        quads += [(IB, q) for q in range(it["q0"], it["q0"] + it["nq"])]
-    assert sorted(quads) == [(IB, q) for IB in range((Tz + 3) // 4) for q in range(IB + 1)]      # every quad of every tile row once
-    assert sum(min(4, Tz - 4 * IB) for IB, _ in quads) == pl["nquads"]
-    assert len(item_ptr) == NW + 1 and item_ptr[0] == 0 and item_ptr[-1] == len(items) and (np.diff(item_ptr) >= 0).all()
     S = (Kc + 3) // 4
-    smask = pl["smask"]
-    assert len(smask) == S + 1 and smask[S] == 0
+    nzpatch = Gpad.reshape(Kc + 1, 4, Tz + 1, 4).any(axis=(1, 3))             # [patch row, tile column]
     sstep = np.zeros((S, Tz + 1), dtype=bool)
     for s in range(S):
         sstep[s] = nzpatch[4 * s:4 * s + 4].any(axis=0)
-    if Tz <= 31:
-        assert [int(x) for x in smask[:S]] == [sum(1 << I for I in range(Tz) if sstep[s, I]) for s in range(S)]
+    klist, items, item_ptr, smask = pl["klist"], pl["items"], pl["item_ptr"], pl["smask"]
+    assert pl["nquads"] == sum(I // 4 + 1 for I in range(Tz))                  # tile row I holds quads 0 .. I // 4
+    if tt:                                                                    # the blocked Gram reads none of them: not built
+        assert len(klist) == len(items) == len(item_ptr) == len(smask) == 0
+    else:
+        assert ((klist >= 0) & (klist <= Kc)).all()
+        quads = []
+        for it in items:
+            IB = it["I0"] // 4
+            assert it["I0"] % 4 == 0 and it["nq"] >= 1
+            lst = klist[it["kptr"]:it["kptr"] + it["klen"]]
+            want = np.nonzero(nzpatch[:Kc, 4 * IB:min(4 * IB + 4, Tz)].any(axis=1))[0]
+            assert np.array_equal(lst, want)                                       # in the list iff a non-zero in the block, all < Kc
+            assert (klist[it["kptr"] + it["klen"]:it["kptr"] + it["klen"] + 8] == Kc).all() and it["kptr"] + it["klen"] + 8 <= len(klist)
+            quads += [(IB, q) for q in range(it["q0"], it["q0"] + it["nq"])]
+        assert sorted(quads) == [(IB, q) for IB in range((Tz + 3) // 4) for q in range(IB + 1)]      # every quad of every tile row once
+        assert sum(min(4, Tz - 4 * IB) for IB, _ in quads) == pl["nquads"]
+        assert len(item_ptr) == NW + 1 and item_ptr[0] == 0 and item_ptr[-1] == len(items) and (np.diff(item_ptr) >= 0).all()
+        assert len(smask) == S + 1 and smask[S] == 0
+        if Tz <= 31:
+            assert [int(x) for x in smask[:S]] == [sum(1 << I for I in range(Tz) if sstep[s, I]) for s in range(S)]
 
     # ---- kernel class, LDS ---------------------------------------------------------------------------------------------------------
     assert pl["lds_bytes"] * pl["wgs_per_cu"] <= LDS_MAX and pl["wgs_per_cu"] >= 1

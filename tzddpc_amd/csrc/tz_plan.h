@@ -52,7 +52,7 @@ struct TzPlan : TzPlanSizes {
   std::vector<int> permc, permr;   // device variable / row i is the caller's permc[i] / permr[i]
   std::vector<int> vpos;           // staircase ordering: device position of v[k, j]; empty = identity
   std::vector<double> P, Gp;
-  std::vector<int> klist, item_ptr, smask;
+  std::vector<int> klist, item_ptr, smask;                             // these three and items: quad class only
   std::vector<IpmItem> items;
   TzEllTable eg, et;               // G x (outputs = rows) and G'v (outputs = columns)
   TzMapTable q, h, par;
@@ -324,9 +324,11 @@ inline int tz_plan_build(const tz_problem_desc& d, TzPlan& pl, std::string& err)
   }
   for (int r = 0; r < nz; ++r) for (int c = 0; c < nz; ++c) if (pl.P[(size_t)r * nzp + c] != 0.0) pl.nP = r + 1;
 
-  tz_plan_items(G, nz, mi, pl);
-  pl.smask.assign((size_t)(Kc + 3) / 4 + 1, 0);
-  if (Tz <= 31) for (int r = 0; r < mi; ++r) for (int c = 0; c < nz; ++c) if (G[(size_t)r * nzp + c] != 0.0) pl.smask[r >> 4] |= 1 << (c >> 2);
+  if (!pl.tt) {                       // quad class only: the tile-triangle Gram works from the units below and reads none of these tables
+    tz_plan_items(G, nz, mi, pl);
+    pl.smask.assign((size_t)(Kc + 3) / 4 + 1, 0);
+    if (Tz <= 31) for (int r = 0; r < mi; ++r) for (int c = 0; c < nz; ++c) if (G[(size_t)r * nzp + c] != 0.0) pl.smask[r >> 4] |= 1 << (c >> 2);
+  }
   // G x: twice as many virtual lanes as rows, so the long rows can be cut up;  G'v: the 192 lanes of waves 1-3 per pass
   pl.eg = tz_plan_ell(byrow, TZ_THREADS, 2 * mi, pl.tt);
   pl.et = tz_plan_ell(bycol, TZ_THREADS - 64, std::max(TZ_THREADS - 64, 2 * nz), pl.tt);
@@ -360,8 +362,6 @@ inline int tz_plan_build(const tz_problem_desc& d, TzPlan& pl, std::string& err)
   const size_t LDS_MAX = 160 * 1024;
   auto fail_lds = [&](size_t need) { TZ_FAIL_TO(err, TZ_ERR_UNSUPPORTED, "not supported: the problem needs %zu bytes of LDS per workgroup (nz=%d, mi=%d); limit is 160 KiB", need, nz, mi); };
   if (pl.tt) {
-    // the item plan and the masks above stay in the kernel's parameter block for this class too, unread: its Gram works from the
-    // units below, and the k-list area of LDS shrinks to nothing
     pl.ntile = Tz * (Tz + 1) / 2;
     pl.nklist = 2;
     const size_t need = tz_plan_place(pl, d.ntheta, tz_plan_ell(byrow, TZ_THREADS, mi, pl.tt), LDS_MAX);

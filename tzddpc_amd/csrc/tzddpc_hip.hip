@@ -67,6 +67,18 @@ struct DevCsr {          // device copy of an affine map of the plan (TzCsr)
   TzCsr view() const { return TzCsr{rows, W, ent.p, c0.p}; }
 };
 
+// What a closed-loop step may start from: the previous step (x / s / lambda in the workspace, valid for prevB trajectories) or the
+// stored start (tz_problem_store_start: solution and multipliers of one reference solve).
+struct WarmState {
+  int prevB = 0;                           // 0: nothing valid
+  bool have_ref = false;
+  DevBuf<double> ref_x, ref_lam;
+  void invalidate() { prevB = 0; }
+  void mark_valid(int B) { prevB = B; }
+  bool valid_for(int B) const { return prevB == B; }
+  void set_ref(bool on) { have_ref = on; if (on) invalidate(); }      // a new stored start replaces the previous step's solution
+};
+
 enum { K_TUBE = 0, K_IPM = 1, K_FINISH = 2, K_PLANT = 3, K_COUNT = 4 };
 
 typedef void (*ipm_fn_t)(IpmParams);
@@ -116,6 +128,86 @@ int use_device(int device) {
 
 }  // namespace
 
+struct tz_genstack {
+  int device = 0, n = 0, m = 0, N = 0, nseg = 0, rec = 0, nchunk = 0;
+  int64_t G = 0;
+  std::vector<int> seg_ptr;                 // literal order
+  DevBuf<double> recs_sorted, recs_lit, recs_mf, recs_mfn, c0, cE, cZ, K, partial, in_e0, in_zeta, o_c, o_rx, o_ru, o_Z;
+  DevBuf<int> src_lit, seg_chunk_ptr;
+  DevBuf<GsChunk> chunks;
+  DevBuf<GsChunkM> chunks_m;                // matrix-core layout (tz_genstack_mfma_kernel): groups of 4 generators, K rows appended
+  bool mfma = false;
+  int rows_mf = 0;                          // rows per generator in recs_mf: n + m (K rows appended) or n (formed in the kernel)
+  size_t pcap = 0;                          // doubles allocated for `partial`
+  bool have_cZ = false;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+};
+
+namespace {
+int gs_inputs(tz_genstack* g, int B, const double* e0, const double* zeta, int mem, const double** de0, const double** dz) {
+  const size_t p = g->n + g->m;
+  if (mem == TZ_MEM_DEVICE) { *de0 = e0; *dz = zeta; return TZ_OK; }
+  if (mem != TZ_MEM_HOST) TZ_FAIL(TZ_ERR_INVALID, "mem must be TZ_MEM_HOST or TZ_MEM_DEVICE");
+  TZ_HIP(g->in_e0.upload(e0, (size_t)B * g->n)); TZ_HIP(g->in_zeta.upload(zeta, (size_t)B * g->N * p));
+  *de0 = g->in_e0.p; *dz = g->in_zeta.p;
+  return TZ_OK;
+}
+
+// room for the per-(chunk, trajectory) partial sums of gs_eval at batch size B (the narrow kernel writes TZ_GS_NARROW_SUB of them)
+int gs_reserve_partial(tz_genstack* g, int B) {
+  const size_t need = (size_t)std::max(g->nchunk, 1) * (B <= 64 ? TZ_GS_NARROW_SUB : 1) * B * (g->n + g->m);
+  if (need > g->pcap) { TZ_HIP(g->partial.alloc(need)); g->pcap = need; }
+  return TZ_OK;
+}
+
+// evaluation of the whole stack for B trajectories, device pointers, on `st`
+int gs_eval(tz_genstack* g, int B, const double* de0, const double* dz, double* dc, double* drx, double* dru, hipStream_t st) {
+  const int n = g->n, m = g->m, p = n + m;
+  GenstackParams q{B, n, m, g->N, g->nseg, g->nchunk, g->rec, g->recs_sorted.p, g->chunks.p, g->K.p, de0, dz, g->partial.p};
+  const dim3 grid((unsigned)g->nchunk, (unsigned)((B + 255) / 256));
+  int nsub = 1;
+  TZ_HIP(hipEventRecord(g->ev0, st));
+  if (g->nchunk > 0 && g->mfma) {
+    // few trajectories: every wave takes all of them and a quarter of the generators (the stack is streamed once: HBM-bound);
+    // many: 256 per workgroup, the stack is re-read from L2 by the tiles of a chunk, which share an XCD
+    const bool split = B <= 64;
+    const int nq = B <= 16 ? 1 : (B <= 32 ? 2 : 4);
+    nsub = split ? TZ_GS_NARROW_SUB : 1;
+    const int ntt = split ? nsub : (B + 255) / 256;
+    const bool krows = g->rows_mf == p || (B > 32 && B <= 64);       // which copy of the stack: K rows appended, or formed in the kernel
+    GenstackMParams qm{B, n, m, g->N, g->nchunk, ntt, nsub, krows ? g->recs_mf.p : g->recs_mfn.p, g->K.p, g->chunks_m.p, de0, dz, g->partial.p};
+    const dim3 gm((unsigned)(((g->nchunk + 7) / 8) * 8 * ntt));
+#define TZ_GS_LAUNCH(RR, PP) do { \
+      if (!split) hipLaunchKernelGGL((tz_genstack_mfma_kernel<RR, PP, 4>), gm, dim3(256), 0, st, qm); \
+      else if (nq == 1) hipLaunchKernelGGL((tz_genstack_mfma_narrow_kernel<RR, PP, 1>), gm, dim3(256), 0, st, qm); \
+      else if (nq == 2) hipLaunchKernelGGL((tz_genstack_mfma_narrow_kernel<RR, PP, 2>), gm, dim3(256), 0, st, qm); \
+      else hipLaunchKernelGGL((tz_genstack_mfma_narrow_kernel<RR, PP, 4>), gm, dim3(256), 0, st, qm); } while (0)
+#define TZ_GS_ROWS(PP) do { if (krows) TZ_GS_LAUNCH(PP, PP); else TZ_GS_LAUNCH(PP - 1, PP); } while (0)      // stored rows: n + m, or n (m = 1)
+    switch (p) {
+      case 3: TZ_GS_ROWS(3); break;
+      case 4: TZ_GS_ROWS(4); break;
+      case 5: TZ_GS_ROWS(5); break;
+      case 6: TZ_GS_ROWS(6); break;
+      default: TZ_GS_ROWS(7); break;
+    }
+#undef TZ_GS_ROWS
+#undef TZ_GS_LAUNCH
+  } else if (g->nchunk > 0) {
+    if (n == 2 && m == 1) hipLaunchKernelGGL((tz_genstack_kernel<2, 1>), grid, dim3(256), 0, st, q);
+    else if (n == 4 && m == 1) hipLaunchKernelGGL((tz_genstack_kernel<4, 1>), grid, dim3(256), 0, st, q);
+    else if (n == 5 && m == 1) hipLaunchKernelGGL((tz_genstack_kernel<5, 1>), grid, dim3(256), 0, st, q);
+    else hipLaunchKernelGGL((tz_genstack_kernel<0, 0>), grid, dim3(256), 0, st, q);
+  }
+  TZ_HIP(hipEventRecord(g->ev1, st));          // the stream kernel alone (what rocprofv3 reports for it); the reduction follows
+  GsReduceParams r{B, n, m, g->N, g->nseg, nsub, g->seg_chunk_ptr.p, g->partial.p, g->c0.p, g->cE.p, g->have_cZ ? g->cZ.p : nullptr, de0, dz, dc, drx, dru};
+  const size_t total = (size_t)B * g->nseg * p;
+  if (B <= 64 && n <= 16) hipLaunchKernelGGL(tz_genstack_reduce16_kernel, dim3((unsigned)((total * 16 + 255) / 256)), dim3(256), 0, st, r);   // few trajectories: latency, not bytes
+  else hipLaunchKernelGGL(tz_genstack_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, r);
+  TZ_HIP(hipGetLastError());
+  return TZ_OK;
+}
+}  // namespace
+
 struct tz_problem {
   int device = 0;
   int n = 0, m = 0, N = 0, nz = 0, mi = 0, ntheta = 0, npar = 0, nc_rows = 0, pmax = 0;
@@ -149,9 +241,7 @@ struct tz_problem {
   int64_t t_count[K_COUNT] = {0, 0, 0, 0};
   int lastB = 0;
   bool prof = TZ_PROFILE;      // diagnostic build: per-phase clocks of workgroup 0 (tz_debug_fetch item 6)
-  bool have_prev = false; int prevB = 0;   // x / s / lambda of the previous closed-loop step are valid for prevB trajectories
-  DevBuf<double> ref_x, ref_lam;          // stored start (tz_problem_store_start): solution and multipliers of one reference solve
-  bool have_ref = false;
+  WarmState warm;
   double warm_floor = 1e-8, warm_gain = 1.0, warm_cap = 1e300, mu_factor = 1e-3, res_factor = 100.0;
   DevBuf<TzGUnit> gunits; DevBuf<int> gunit_ptr;
   DevBuf<int> vpos;            // staircase ordering (tile-triangle class): device position of v[k, j]; null = identity
@@ -163,7 +253,12 @@ struct tz_problem {
   DevBuf<unsigned long long> prof_buf, work_buf;
 };
 
-extern "C" int tube_stack_theta(tz_problem* p, int B, const double* d_e0, hipStream_t st);   // literal problems: theta from the attached stack (defined with the K1g entry points)
+__global__ void tz_seed_kernel(int B, int nz, int mi, const double* rx, const double* rl, double* x, double* lam, int* prev_status, int* iters, int* shift_state) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < (size_t)B * nz) x[i] = rx[i % nz];
+  if (i < (size_t)B * mi) lam[i] = rl[i % mi];
+  if (i < (size_t)B) { prev_status[i] = 0; iters[i] = 0; shift_state[i] = -2; }      // -2: stored start (tz_ipm_kernel: taken unshifted, then the shifted regime)
+}
 
 namespace {
 
@@ -194,7 +289,7 @@ int ensure_workspace(tz_problem* p, int B) {
   TZ_HIP(p->st_xbar.alloc(b * p->n));
   TZ_HIP(p->st_e.alloc(b * p->n));
   p->Bcap = B;
-  p->have_prev = false;
+  p->warm.invalidate();
   return TZ_OK;
 }
 
@@ -251,33 +346,63 @@ IpmParams ipm_params(tz_problem* p, int B, int* d_status, int* d_iters, bool war
   ip.warm_gain = p->warm_gain; ip.warm_cap = p->warm_cap; ip.aff_thr = 0.99; ip.aff_mu = 1e-3;
   ip.prev_status = warm ? p->prev_status.p : nullptr;
   ip.status_copy = track_prev ? p->prev_status.p : nullptr;
-  ip.F.on = 0;
   return ip;
 }
 
-// One closed-loop step of B trajectories in ONE launch (tz_ipm_kernel with F.on): tube, parameter maps, interior point,
-// recovery / objective and plant update; theta, q and h never reach HBM.  Same arithmetic as launch_solve + launch_plant.
-struct StepStrides { size_t w, u, x, cost; };     // element offsets per closed-loop step inside one launch
-int launch_step_fused(tz_problem* p, int B, double* d_x, double* d_xbar, double* d_e, const double* d_w, size_t w_stride,
-                      const double* d_A, const double* d_Bm, double* d_u, size_t u_stride, double* d_xout, size_t x_stride,
-                      double* d_cost, size_t cost_stride, int* d_status, int* d_sticky, bool warm,
-                      int nsteps = 1, StepStrides ss = StepStrides{0, 0, 0, 0}, bool sticky_fresh = false) {
-  p->lastB = B;
-  Timer tm(p, K_IPM);
-  IpmParams ip = ipm_params(p, B, d_status, p->iters.p, warm, true);
-  FuseParams& F = ip.F;
-  F.on = 1; F.npar = p->npar; F.ntheta = p->ntheta; F.lean_epilogue = p->pl.lean_epilogue ? 1 : 0; F.sticky_fresh = sticky_fresh ? 1 : 0;
-  F.nsteps = nsteps; F.warm_steps = 1; ip.warm_steps = F.warm_steps;
-  F.w_step = ss.w; F.u_step = ss.u; F.x_step = ss.x; F.cost_step = ss.cost;
-  F.tube = TubeParams{B, p->n, p->m, p->N, p->pmax, p->ntheta, p->CKpow.p, p->Ttube.p, p->power.p, d_xbar, d_e, nullptr, nullptr};
-  F.qmap = p->q.view(); F.hmap = p->h.view(); F.parmap = p->par.view(); F.par_lo = p->par_lo.p; F.par_hi = p->par_hi.p;
-  F.fin = FinishParams{B, p->n, p->m, p->N, p->nz, p->mi, p->pl.nzp, p->nc_rows, p->P.p, p->Dz.p, p->Phi.p, p->Gam.p,
-                       p->r1.p, p->R2.p, p->r0, p->cost_scale, p->row_of.p, p->act_scale.p, d_xbar, nullptr, nullptr, nullptr, nullptr,
-                       d_status, nsteps > 1 ? nullptr : p->v.p, nsteps > 1 ? nullptr : p->xbar.p, d_cost, nullptr, cost_stride, p->vpos.p,
-                       p->rec0.p, p->recx.p, p->recy.p};
-  F.plant = PlantParams{B, p->n, p->m, p->N, p->K.p, d_A, d_Bm, nullptr, nullptr, d_w, w_stride, d_status, d_x, d_xbar, d_e,
-                        d_u, u_stride, d_xout, x_stride, d_sticky};
-  hipLaunchKernelGGL(p->ipm_fn, dim3(B), dim3(TZ_THREADS), p->pl.lds_bytes, p->stream, ip);
+// Launch blocks: the fields that come from the problem, by name; the launch sites add their pointers.
+TubeParams tube_params(const tz_problem* p, int B) {
+  TubeParams t{};
+  t.B = B; t.n = p->n; t.m = p->m; t.N = p->N; t.pmax = p->pmax; t.ntheta = p->ntheta;
+  t.CKpow = p->CKpow.p; t.T = p->Ttube.p; t.power = p->power.p;
+  return t;
+}
+
+FinishParams finish_params(const tz_problem* p, int B) {
+  FinishParams f{};
+  f.B = B; f.n = p->n; f.m = p->m; f.N = p->N; f.nz = p->nz; f.mi = p->mi; f.nzp = p->pl.nzp; f.nc_rows = p->nc_rows;
+  f.P = p->P.p; f.Dz = p->Dz.p; f.Phi = p->Phi.p; f.Gam = p->Gam.p; f.r1 = p->r1.p; f.R2 = p->R2.p; f.r0 = p->r0; f.cost_scale = p->cost_scale;
+  f.row_of = p->row_of.p; f.act_scale = p->act_scale.p; f.vpos = p->vpos.p; f.rec0 = p->rec0.p; f.recx = p->recx.p; f.recy = p->recy.p;
+  return f;
+}
+
+// What a closed-loop call reads and writes, all in device memory.  Element [b] of step t of a strided array is at
+// base + b * stride + t * step.
+struct ClosedLoopIO {
+  double* x; double* xbar; double* e;                  // B x n each: the state, advanced in place
+  const double* w; size_t w_stride, w_step;            // disturbances
+  const double* A; const double* Bm;                   // the true plant
+  double* u_out; size_t u_stride, u_step;              // may be null
+  double* x_out; size_t x_stride, x_step;              // may be null: copy of x+
+  double* cost; size_t cost_stride, cost_step;         // cost_step 0: one slot per trajectory, overwritten by every step
+  int* status;                                         // B: solver status of the step, overwritten by every step
+  int* sticky;                                         // may be null; B: first non-zero status of the run
+  bool sticky_fresh;                                   // the run clears sticky itself (the caller has not)
+  bool fresh;                                          // a loop of its own (tz_simulate_batch): starts without a previous step and marks none
+};
+
+PlantParams plant_params(const tz_problem* p, int B, const ClosedLoopIO& io) {        // step 0; v and xbar_pred stay null (fused step)
+  PlantParams q{};
+  q.B = B; q.n = p->n; q.m = p->m; q.N = p->N; q.K = p->K.p; q.A = io.A; q.Bm = io.Bm;
+  q.w = io.w; q.w_stride = io.w_stride; q.status = io.status; q.x = io.x; q.xbar = io.xbar; q.e = io.e;
+  q.u_out = io.u_out; q.u_stride = io.u_stride; q.x_out = io.x_out; q.x_stride = io.x_stride; q.sticky = io.sticky;
+  return q;
+}
+
+// literal problems: theta from the attached generator stack
+int tube_stack_theta(tz_problem* p, int B, const double* d_e0, hipStream_t st) {
+  tz_genstack* g = p->tube_stack;
+  const int n = p->n, m = p->m, pq = n + m;
+  if (B > p->ts_cap) {
+    TZ_HIP(p->ts_zeta.alloc((size_t)B * g->N * pq)); TZ_HIP(hipMemset(p->ts_zeta.p, 0, (size_t)B * g->N * pq * sizeof(double)));
+    TZ_HIP(p->ts_c.alloc((size_t)B * g->nseg * n)); TZ_HIP(p->ts_rx.alloc((size_t)B * g->nseg * n)); TZ_HIP(p->ts_ru.alloc((size_t)B * g->nseg * m));
+    p->ts_cap = B;
+  }
+  if (int rcp = gs_reserve_partial(g, B)) return rcp;
+  int rc = gs_eval(g, B, d_e0, p->ts_zeta.p, p->ts_c.p, p->ts_rx.p, p->ts_ru.p, st);
+  if (rc) return rc;
+  ThetaStackParams q{B, n, m, p->N, g->nseg, p->ntheta, p->ts_c.p, p->ts_rx.p, p->ts_ru.p, p->theta.p};
+  const size_t total = (size_t)B * p->N * (2 * n + m);
+  hipLaunchKernelGGL(tz_theta_stack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, q);
   TZ_HIP(hipGetLastError());
   return TZ_OK;
 }
@@ -289,7 +414,8 @@ int launch_solve(tz_problem* p, int B, const double* d_xbar0, const double* d_e0
   p->lastB = B;
   {
     Timer tm(p, K_TUBE);
-    TubeParams tp{B, p->n, p->m, p->N, p->pmax, p->ntheta, p->CKpow.p, p->Ttube.p, p->power.p, d_xbar0, d_e0, p->theta.p, p->prestatus.p};
+    TubeParams tp = tube_params(p, B);
+    tp.xbar0 = d_xbar0; tp.e0 = d_e0; tp.theta = p->theta.p; tp.prestatus = p->prestatus.p;
     hipLaunchKernelGGL(tz_tube_kernel, dim3(B), dim3(64), 0, st, tp);
     if (p->tube_stack) { int rc = tube_stack_theta(p, B, d_e0, st); if (rc) return rc; }
     AffineParams ap{B, p->ntheta, p->nz, p->mi, p->npar, p->q.view(), p->h.view(), p->par.view(), p->par_lo.p, p->par_hi.p,
@@ -301,30 +427,74 @@ int launch_solve(tz_problem* p, int B, const double* d_xbar0, const double* d_e0
     Timer tm(p, K_IPM);
     IpmParams ip = ipm_params(p, B, d_status, d_iters, warm, track_prev);
     // active-set readout (slack < multiplier) needs the complementarity products well below the slacks: three decades below the
-    // stopping target, but never below 1e-6 tol (1e-16 at the default tolerance: what the loosest calibrated target used to give --
-    // with the tighter targets of round 3 an unbounded 1e-3 asked degenerate problems for mu = 1e-18 and they ended TZ_NUMERICAL)
+    // stopping target, but never below 1e-6 tol (1e-16 at the default tolerance) -- an unbounded 1e-3 under a tight stopping target
+    // asked degenerate problems for mu = 1e-18 and they ended TZ_NUMERICAL
     if (d_active) { const double f = std::min(1.0, std::max(1e-3, 1e-6 * p->tol / ip.mu_tol)); ip.mu_tol *= f; ip.mu_floor *= f; }
     hipLaunchKernelGGL(p->ipm_fn, dim3(B), dim3(TZ_THREADS), p->pl.lds_bytes, st, ip);
   }
   {
     Timer tm(p, K_FINISH);
-    FinishParams fp{B, p->n, p->m, p->N, p->nz, p->mi, p->pl.nzp, p->nc_rows, p->P.p, p->Dz.p, p->Phi.p, p->Gam.p,
-                    p->r1.p, p->R2.p, p->r0, p->cost_scale, p->row_of.p, p->act_scale.p, d_xbar0, p->qv.p, p->x.p, p->s.p, p->lam.p,
-                    d_status, d_v, d_xbar, d_cost, d_active, cost_stride, p->vpos.p, p->rec0.p, p->recx.p, p->recy.p};
+    FinishParams fp = finish_params(p, B);
+    fp.xbar0 = d_xbar0; fp.q = p->qv.p; fp.x = p->x.p; fp.s = p->s.p; fp.lam = p->lam.p; fp.status = d_status;
+    fp.v = d_v; fp.xbar = d_xbar; fp.cost = d_cost; fp.active = d_active; fp.cost_stride = cost_stride;
     hipLaunchKernelGGL(tz_finish_kernel, dim3(B), dim3(64), 0, st, fp);
   }
   TZ_HIP(hipGetLastError());
   return TZ_OK;
 }
 
-int launch_plant(tz_problem* p, int B, const double* d_A, const double* d_Bm, const double* d_w, size_t w_stride,
-                 const double* d_v, const double* d_xbar_pred, const int* d_status,
-                 double* d_x, double* d_xbar, double* d_e, double* d_u, size_t u_stride, double* d_xout, size_t x_stride, int* d_sticky) {
-  Timer tm(p, K_PLANT);
-  PlantParams pp{B, p->n, p->m, p->N, p->K.p, d_A, d_Bm, d_v, d_xbar_pred, d_w, w_stride, d_status, d_x, d_xbar, d_e,
-                 d_u, u_stride, d_xout, x_stride, d_sticky};
-  hipLaunchKernelGGL(tz_plant_kernel, dim3((B + 63) / 64), dim3(64), 0, p->stream, pp);
+// What a closed-loop launch starts from: the previous step's solution; else the stored start, seeded into every trajectory (the solution
+// of ONE reference solve, tz_problem_store_start: the caller's point, typically the centre of X0 with e0 = 0); else the cold point.
+int closed_loop_warm(tz_problem* p, int B, bool* warm) {
+  const bool prev = p->warm.valid_for(B);
+  *warm = prev || p->warm.have_ref;
+  if (prev || !p->warm.have_ref) return TZ_OK;
+  const size_t total = (size_t)B * std::max(p->nz, p->mi);
+  hipLaunchKernelGGL(tz_seed_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, p->stream, B, p->nz, p->mi, p->warm.ref_x.p, p->warm.ref_lam.p,
+                     p->x.p, p->lam.p, p->prev_status.p, p->iters.p, p->shift_state.p);
   TZ_HIP(hipGetLastError());
+  p->warm.mark_valid(B);
+  return TZ_OK;
+}
+
+// K closed-loop steps of B trajectories: what tz_mpc_step, tz_mpc_run and tz_simulate_batch do once their arguments are on the device.
+// Fused: ONE launch of tz_ipm_kernel with F.on does tube, parameter maps, interior point, recovery / objective and plant update of all
+// K steps; theta, q and h never reach HBM and the state never leaves the workgroup.  Otherwise launch_solve and tz_plant_kernel per
+// step: same arithmetic, four kernels.
+int run_closed_loop(tz_problem* p, int B, int K, const ClosedLoopIO& io) {
+  if (io.fresh) p->warm.invalidate();
+  bool warm = false;
+  if (int rc = closed_loop_warm(p, B, &warm)) return rc;
+  if (p->fuse_enabled) {
+    p->lastB = B;
+    Timer tm(p, K_IPM);
+    IpmParams ip = ipm_params(p, B, io.status, p->iters.p, warm, true);
+    FuseParams& F = ip.F;
+    F.on = 1; F.npar = p->npar; F.ntheta = p->ntheta; F.lean_epilogue = p->pl.lean_epilogue ? 1 : 0; F.sticky_fresh = io.sticky_fresh ? 1 : 0;
+    F.nsteps = K; F.warm_steps = 1; ip.warm_steps = F.warm_steps;
+    F.w_step = io.w_step; F.u_step = io.u_step; F.x_step = io.x_step; F.cost_step = io.cost_step;
+    F.tube = tube_params(p, B); F.tube.xbar0 = io.xbar; F.tube.e0 = io.e;                   // theta stays in LDS
+    F.qmap = p->q.view(); F.hmap = p->h.view(); F.parmap = p->par.view(); F.par_lo = p->par_lo.p; F.par_hi = p->par_hi.p;
+    F.fin = finish_params(p, B);
+    F.fin.xbar0 = io.xbar; F.fin.status = io.status; F.fin.cost = io.cost; F.fin.cost_stride = io.cost_stride;
+    if (K == 1) { F.fin.v = p->v.p; F.fin.xbar = p->xbar.p; }                                // a single step also leaves its prediction
+    F.plant = plant_params(p, B, io);
+    hipLaunchKernelGGL(p->ipm_fn, dim3(B), dim3(TZ_THREADS), p->pl.lds_bytes, p->stream, ip);
+    TZ_HIP(hipGetLastError());
+  } else {
+    if (io.sticky && io.sticky_fresh) TZ_HIP(hipMemsetAsync(io.sticky, 0, (size_t)B * sizeof(int), p->stream));
+    for (int t = 0; t < K; ++t) {
+      if (int rc = launch_solve(p, B, io.xbar, io.e, p->v.p, p->xbar.p, io.cost + t * io.cost_step, io.status, p->iters.p, nullptr, io.cost_stride, warm || t > 0, true)) return rc;
+      Timer tm(p, K_PLANT);
+      PlantParams pp = plant_params(p, B, io);
+      pp.v = p->v.p; pp.xbar_pred = p->xbar.p; pp.w += t * io.w_step;          // v and the prediction launch_solve left in the workspace
+      if (pp.u_out) pp.u_out += t * io.u_step;
+      if (pp.x_out) pp.x_out += t * io.x_step;
+      hipLaunchKernelGGL(tz_plant_kernel, dim3((B + 63) / 64), dim3(64), 0, p->stream, pp);
+      TZ_HIP(hipGetLastError());
+    }
+  }
+  if (!io.fresh) p->warm.mark_valid(B);
   return TZ_OK;
 }
 
@@ -406,21 +576,6 @@ int tz_adversary_batch(int device, int32_t S, int32_t n, int32_t ngen, const dou
   return gain_batch(true, device, S, n, ngen, M0, H, beta0, max_iter, beta, fro, steps);
 }
 
-struct tz_genstack {
-  int device = 0, n = 0, m = 0, N = 0, nseg = 0, rec = 0, nchunk = 0;
-  int64_t G = 0;
-  std::vector<int> seg_ptr;                 // literal order
-  DevBuf<double> recs_sorted, recs_lit, recs_mf, recs_mfn, c0, cE, cZ, K, partial, in_e0, in_zeta, o_c, o_rx, o_ru, o_Z;
-  DevBuf<int> src_lit, seg_chunk_ptr;
-  DevBuf<GsChunk> chunks;
-  DevBuf<GsChunkM> chunks_m;                // matrix-core layout (tz_genstack_mfma_kernel): groups of 4 generators, K rows appended
-  bool mfma = false;
-  int rows_mf = 0;                          // rows per generator in recs_mf: n + m (K rows appended) or n (formed in the kernel)
-  size_t pcap = 0;                          // doubles allocated for `partial`
-  bool have_cZ = false;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-};
-
 int tz_genstack_create(int device, const tz_genstack_desc* d, tz_genstack** out) {
   if (!d || !out) TZ_FAIL(TZ_ERR_INVALID, "null argument");
   int rc = tz_genstack_plan_check(*d, g_err);
@@ -462,79 +617,6 @@ int tz_genstack_info(tz_genstack* g, int64_t* generators, int64_t* stack_bytes, 
   return TZ_OK;
 }
 
-namespace {
-int gs_inputs(tz_genstack* g, int B, const double* e0, const double* zeta, int mem, const double** de0, const double** dz) {
-  const size_t p = g->n + g->m;
-  if (mem == TZ_MEM_DEVICE) { *de0 = e0; *dz = zeta; return TZ_OK; }
-  if (mem != TZ_MEM_HOST) TZ_FAIL(TZ_ERR_INVALID, "mem must be TZ_MEM_HOST or TZ_MEM_DEVICE");
-  TZ_HIP(g->in_e0.upload(e0, (size_t)B * g->n)); TZ_HIP(g->in_zeta.upload(zeta, (size_t)B * g->N * p));
-  *de0 = g->in_e0.p; *dz = g->in_zeta.p;
-  return TZ_OK;
-}
-}  // namespace
-
-// room for the per-(chunk, trajectory) partial sums of gs_eval at batch size B (the narrow kernel writes TZ_GS_NARROW_SUB of them)
-static int gs_reserve_partial(tz_genstack* g, int B) {
-  const size_t need = (size_t)std::max(g->nchunk, 1) * (B <= 64 ? TZ_GS_NARROW_SUB : 1) * B * (g->n + g->m);
-  if (need > g->pcap) { TZ_HIP(g->partial.alloc(need)); g->pcap = need; }
-  return TZ_OK;
-}
-
-// evaluation of the whole stack for B trajectories, device pointers, on `st`
-static int gs_eval(tz_genstack* g, int B, const double* de0, const double* dz, double* dc, double* drx, double* dru, hipStream_t st) {
-  const int n = g->n, m = g->m, p = n + m;
-  GenstackParams q{B, n, m, g->N, g->nseg, g->nchunk, g->rec, g->recs_sorted.p, g->chunks.p, g->K.p, de0, dz, g->partial.p};
-  const dim3 grid((unsigned)g->nchunk, (unsigned)((B + 255) / 256));
-  int nsub = 1;
-  TZ_HIP(hipEventRecord(g->ev0, st));
-  if (g->nchunk > 0 && g->mfma) {
-    // few trajectories: every wave takes all of them and a quarter of the generators (the stack is streamed once: HBM-bound);
-    // many: 256 per workgroup, the stack is re-read from L2 by the tiles of a chunk, which share an XCD
-    const bool split = B <= 64;
-    const int nq = B <= 16 ? 1 : (B <= 32 ? 2 : 4);
-    nsub = split ? TZ_GS_NARROW_SUB : 1;
-    const int ntt = split ? nsub : (B + 255) / 256;
-    const bool krows = g->rows_mf == p || (B > 32 && B <= 64);       // which copy of the stack: K rows appended, or formed in the kernel
-    GenstackMParams qm{B, n, m, g->N, g->nchunk, ntt, nsub, krows ? g->recs_mf.p : g->recs_mfn.p, g->K.p, g->chunks_m.p, de0, dz, g->partial.p};
-    const dim3 gm((unsigned)(((g->nchunk + 7) / 8) * 8 * ntt));
-#define TZ_GS_LAUNCH(RR, PP) do { \
-      if (!split) hipLaunchKernelGGL((tz_genstack_mfma_kernel<RR, PP, 4>), gm, dim3(256), 0, st, qm); \
-      else if (nq == 1) hipLaunchKernelGGL((tz_genstack_mfma_narrow_kernel<RR, PP, 1>), gm, dim3(256), 0, st, qm); \
-      else if (nq == 2) hipLaunchKernelGGL((tz_genstack_mfma_narrow_kernel<RR, PP, 2>), gm, dim3(256), 0, st, qm); \
-      else hipLaunchKernelGGL((tz_genstack_mfma_narrow_kernel<RR, PP, 4>), gm, dim3(256), 0, st, qm); } while (0)
-    if (krows) {
-      switch (p) {
-        case 3: TZ_GS_LAUNCH(3, 3); break;
-        case 4: TZ_GS_LAUNCH(4, 4); break;
-        case 5: TZ_GS_LAUNCH(5, 5); break;
-        case 6: TZ_GS_LAUNCH(6, 6); break;
-        default: TZ_GS_LAUNCH(7, 7); break;
-      }
-    } else {
-      switch (p) {
-        case 3: TZ_GS_LAUNCH(2, 3); break;
-        case 4: TZ_GS_LAUNCH(3, 4); break;
-        case 5: TZ_GS_LAUNCH(4, 5); break;
-        case 6: TZ_GS_LAUNCH(5, 6); break;
-        default: TZ_GS_LAUNCH(6, 7); break;
-      }
-    }
-#undef TZ_GS_LAUNCH
-  } else if (g->nchunk > 0) {
-    if (n == 2 && m == 1) hipLaunchKernelGGL((tz_genstack_kernel<2, 1>), grid, dim3(256), 0, st, q);
-    else if (n == 4 && m == 1) hipLaunchKernelGGL((tz_genstack_kernel<4, 1>), grid, dim3(256), 0, st, q);
-    else if (n == 5 && m == 1) hipLaunchKernelGGL((tz_genstack_kernel<5, 1>), grid, dim3(256), 0, st, q);
-    else hipLaunchKernelGGL((tz_genstack_kernel<0, 0>), grid, dim3(256), 0, st, q);
-  }
-  TZ_HIP(hipEventRecord(g->ev1, st));          // the stream kernel alone (what rocprofv3 reports for it); the reduction follows
-  GsReduceParams r{B, n, m, g->N, g->nseg, nsub, g->seg_chunk_ptr.p, g->partial.p, g->c0.p, g->cE.p, g->have_cZ ? g->cZ.p : nullptr, de0, dz, dc, drx, dru};
-  const size_t total = (size_t)B * g->nseg * p;
-  if (B <= 64 && n <= 16) hipLaunchKernelGGL(tz_genstack_reduce16_kernel, dim3((unsigned)((total * 16 + 255) / 256)), dim3(256), 0, st, r);   // few trajectories: latency, not bytes
-  else hipLaunchKernelGGL(tz_genstack_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, r);
-  TZ_HIP(hipGetLastError());
-  return TZ_OK;
-}
-
 int tz_genstack_intervals(tz_genstack* g, int32_t B, const double* e0, const double* zeta,
                           double* centre, double* rad_x, double* rad_u, double* kernel_ms, int mem) {
   if (!g || !e0 || !zeta || !centre || !rad_x || !rad_u) TZ_FAIL(TZ_ERR_INVALID, "null argument");
@@ -563,24 +645,6 @@ int tz_genstack_intervals(tz_genstack* g, int32_t B, const double* e0, const dou
     TZ_HIP(hipEventElapsedTime(&ms, g->ev0, g->ev1));
     *kernel_ms = ms;
   }
-  return TZ_OK;
-}
-
-int tube_stack_theta(tz_problem* p, int B, const double* d_e0, hipStream_t st) {
-  tz_genstack* g = p->tube_stack;
-  const int n = p->n, m = p->m, pq = n + m;
-  if (B > p->ts_cap) {
-    TZ_HIP(p->ts_zeta.alloc((size_t)B * g->N * pq)); TZ_HIP(hipMemset(p->ts_zeta.p, 0, (size_t)B * g->N * pq * sizeof(double)));
-    TZ_HIP(p->ts_c.alloc((size_t)B * g->nseg * n)); TZ_HIP(p->ts_rx.alloc((size_t)B * g->nseg * n)); TZ_HIP(p->ts_ru.alloc((size_t)B * g->nseg * m));
-    p->ts_cap = B;
-  }
-  if (int rcp = gs_reserve_partial(g, B)) return rcp;
-  int rc = gs_eval(g, B, d_e0, p->ts_zeta.p, p->ts_c.p, p->ts_rx.p, p->ts_ru.p, st);
-  if (rc) return rc;
-  ThetaStackParams q{B, n, m, p->N, g->nseg, p->ntheta, p->ts_c.p, p->ts_rx.p, p->ts_ru.p, p->theta.p};
-  const size_t total = (size_t)B * p->N * (2 * n + m);
-  hipLaunchKernelGGL(tz_theta_stack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, q);
-  TZ_HIP(hipGetLastError());
   return TZ_OK;
 }
 
@@ -705,7 +769,7 @@ int tz_solve_batch(tz_problem* p, int32_t B, const double* xbar0, const double* 
   TZ_HIP(hipSetDevice(p->device));
   int rc = ensure_workspace(p, B);
   if (rc) return rc;
-  p->have_prev = false;
+  p->warm.invalidate();
   const size_t bn = (size_t)B * p->n * sizeof(double);
   if (mem == TZ_MEM_DEVICE) {
     return launch_solve(p, B, xbar0, e0, v, xbar, cost, status, iters, active);
@@ -726,32 +790,9 @@ int tz_solve_batch(tz_problem* p, int32_t B, const double* xbar0, const double* 
   return TZ_OK;
 }
 
-// Stored start: the first closed-loop step of a trajectory that has no previous solution starts from the solution of ONE reference
-// solve (tz_problem_store_start: the caller's point, typically the centre of X0 with e0 = 0) instead of from the cold point.
-__global__ void tz_seed_kernel(int B, int nz, int mi, const double* rx, const double* rl, double* x, double* lam, int* prev_status, int* iters, int* shift_state) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < (size_t)B * nz) x[i] = rx[i % nz];
-  if (i < (size_t)B * mi) lam[i] = rl[i % mi];
-  if (i < (size_t)B) { prev_status[i] = 0; iters[i] = 0; shift_state[i] = -2; }      // -2: stored start (tz_ipm_kernel: taken unshifted, then the shifted regime)
-}
-static int seed_warm(tz_problem* p, int B) {
-  const size_t total = (size_t)B * std::max(p->nz, p->mi);
-  hipLaunchKernelGGL(tz_seed_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, p->stream, B, p->nz, p->mi, p->ref_x.p, p->ref_lam.p,
-                     p->x.p, p->lam.p, p->prev_status.p, p->iters.p, p->shift_state.p);
-  TZ_HIP(hipGetLastError());
-  p->have_prev = true; p->prevB = B;
-  return TZ_OK;
-}
-// warm-start state of a closed-loop launch: the previous step's, else the stored start's, else none (cold)
-static int closed_loop_warm(tz_problem* p, int B, bool* warm) {
-  *warm = p->have_prev && p->prevB == B;
-  if (!*warm && p->have_ref) { int rc = seed_warm(p, B); if (rc) return rc; *warm = true; }
-  return TZ_OK;
-}
-
 int tz_problem_store_start(tz_problem* p, const double* xbar0, const double* e0) {
   if (!p) TZ_FAIL(TZ_ERR_INVALID, "null problem");
-  if (!xbar0 || !e0) { p->have_ref = false; return TZ_OK; }                       // NULL: forget the stored start
+  if (!xbar0 || !e0) { p->warm.set_ref(false); return TZ_OK; }                       // NULL: forget the stored start
   TZ_HIP(hipSetDevice(p->device));
   int rc = ensure_workspace(p, 1);
   if (rc) return rc;
@@ -763,11 +804,11 @@ int tz_problem_store_start(tz_problem* p, const double* xbar0, const double* e0)
   TZ_HIP(hipMemcpyAsync(&st, p->status.p, sizeof(int), hipMemcpyDeviceToHost, p->stream));
   TZ_HIP(hipStreamSynchronize(p->stream));
   if (st != 0) TZ_FAIL(TZ_ERR_INVALID, "the reference point is not solvable (status %d): no start stored", st);
-  TZ_HIP(p->ref_x.alloc((size_t)p->nz)); TZ_HIP(p->ref_lam.alloc((size_t)p->mi));
-  TZ_HIP(hipMemcpyAsync(p->ref_x.p, p->x.p, (size_t)p->nz * sizeof(double), hipMemcpyDeviceToDevice, p->stream));
-  TZ_HIP(hipMemcpyAsync(p->ref_lam.p, p->lam.p, (size_t)p->mi * sizeof(double), hipMemcpyDeviceToDevice, p->stream));
+  TZ_HIP(p->warm.ref_x.alloc((size_t)p->nz)); TZ_HIP(p->warm.ref_lam.alloc((size_t)p->mi));
+  TZ_HIP(hipMemcpyAsync(p->warm.ref_x.p, p->x.p, (size_t)p->nz * sizeof(double), hipMemcpyDeviceToDevice, p->stream));
+  TZ_HIP(hipMemcpyAsync(p->warm.ref_lam.p, p->lam.p, (size_t)p->mi * sizeof(double), hipMemcpyDeviceToDevice, p->stream));
   TZ_HIP(hipStreamSynchronize(p->stream));
-  p->have_ref = true; p->have_prev = false;
+  p->warm.set_ref(true);
   return TZ_OK;
 }
 
@@ -776,20 +817,12 @@ int tz_mpc_step(tz_problem* p, int32_t B, double* x, double* xbar, double* e, co
   if (!p || !x || !xbar || !e || !w || !A_true || !B_true || !cost || !status) TZ_FAIL(TZ_ERR_INVALID, "null argument");
   if (B <= 0) TZ_FAIL(TZ_ERR_INVALID, "batch size must be positive");
   TZ_HIP(hipSetDevice(p->device));
-  int rc = ensure_workspace(p, B);
-  if (rc) return rc;
-  bool warm = false;
-  if ((rc = closed_loop_warm(p, B, &warm))) return rc;
-  if (p->fuse_enabled) {
-    rc = launch_step_fused(p, B, x, xbar, e, w, (size_t)p->n, A_true, B_true, u_out, (size_t)p->m, nullptr, 0, cost, 1, status, nullptr, warm);
-    if (rc == TZ_OK) { p->have_prev = true; p->prevB = B; }
-    return rc;
-  }
-  rc = launch_solve(p, B, xbar, e, p->v.p, p->xbar.p, cost, status, p->iters.p, nullptr, 1, warm, true);
-  if (rc) return rc;
-  p->have_prev = true; p->prevB = B;
-  return launch_plant(p, B, A_true, B_true, w, (size_t)p->n, p->v.p, p->xbar.p, status, x, xbar, e,
-                      u_out, (size_t)p->m, nullptr, 0, nullptr);
+  if (int rc = ensure_workspace(p, B)) return rc;
+  ClosedLoopIO io{};
+  io.x = x; io.xbar = xbar; io.e = e; io.w = w; io.w_stride = (size_t)p->n; io.A = A_true; io.Bm = B_true;
+  io.u_out = u_out; io.u_stride = (size_t)p->m; io.cost = cost; io.cost_stride = 1;
+  io.status = status;                       // the solver status itself; no sticky record
+  return run_closed_loop(p, B, 1, io);
 }
 
 int tz_mpc_run(tz_problem* p, int32_t B, int32_t K, double* x, double* xbar, double* e, const double* w,
@@ -797,29 +830,12 @@ int tz_mpc_run(tz_problem* p, int32_t B, int32_t K, double* x, double* xbar, dou
   if (!p || !x || !xbar || !e || !w || !A_true || !B_true || !cost || !status) TZ_FAIL(TZ_ERR_INVALID, "null argument");
   if (B <= 0 || K <= 0) TZ_FAIL(TZ_ERR_INVALID, "B and K must be positive");
   TZ_HIP(hipSetDevice(p->device));
-  int rc = ensure_workspace(p, B);
-  if (rc) return rc;
-  if (p->fuse_enabled) {                    // all K steps of every trajectory in ONE launch: the state never leaves the workgroup
-    bool warm = false;
-    if ((rc = closed_loop_warm(p, B, &warm))) return rc;
-    rc = launch_step_fused(p, B, x, xbar, e, w, (size_t)p->n, A_true, B_true, u_out, (size_t)p->m, nullptr, 0,
-                           cost, 1, p->status.p, status, warm, K, StepStrides{(size_t)B * p->n, 0, 0, 0}, true);   // `status` cleared by the kernel
-    if (rc) return rc;
-    p->have_prev = true; p->prevB = B;
-    return TZ_OK;
-  }
-  TZ_HIP(hipMemsetAsync(status, 0, (size_t)B * sizeof(int), p->stream));
-  for (int t = 0; t < K; ++t) {
-    bool warm = false;
-    if ((rc = closed_loop_warm(p, B, &warm))) return rc;
-    rc = launch_solve(p, B, xbar, e, p->v.p, p->xbar.p, cost, p->status.p, p->iters.p, nullptr, 1, warm, true);
-    if (rc) return rc;
-    p->have_prev = true; p->prevB = B;
-    rc = launch_plant(p, B, A_true, B_true, w + (size_t)t * B * p->n, (size_t)p->n, p->v.p, p->xbar.p, p->status.p, x, xbar, e,
-                      u_out, (size_t)p->m, nullptr, 0, status);
-    if (rc) return rc;
-  }
-  return TZ_OK;
+  if (int rc = ensure_workspace(p, B)) return rc;
+  ClosedLoopIO io{};
+  io.x = x; io.xbar = xbar; io.e = e; io.w = w; io.w_stride = (size_t)p->n; io.w_step = (size_t)B * p->n; io.A = A_true; io.Bm = B_true;
+  io.u_out = u_out; io.u_stride = (size_t)p->m; io.cost = cost; io.cost_stride = 1;      // u and cost of the last step survive
+  io.status = p->status.p; io.sticky = status; io.sticky_fresh = true;                   // the caller sees the first failure of the run
+  return run_closed_loop(p, B, K, io);
 }
 
 int tz_simulate_batch(tz_problem* p, int32_t B, int32_t T, const double* x0, const double* noise,
@@ -828,11 +844,9 @@ int tz_simulate_batch(tz_problem* p, int32_t B, int32_t T, const double* x0, con
   if (!p || !x0 || !noise || !A_true || !B_true || !x_traj || !u_traj || !status) TZ_FAIL(TZ_ERR_INVALID, "null argument");
   if (B <= 0 || T <= 0) TZ_FAIL(TZ_ERR_INVALID, "B and T must be positive");
   TZ_HIP(hipSetDevice(p->device));
-  int rc = ensure_workspace(p, B);
-  if (rc) return rc;
+  if (int rc = ensure_workspace(p, B)) return rc;
   hipStream_t st = p->stream;
   const int n = p->n, m = p->m;
-  p->have_prev = false;
   const bool host = (mem == TZ_MEM_HOST);
   if (!host && mem != TZ_MEM_DEVICE) TZ_FAIL(TZ_ERR_INVALID, "mem must be TZ_MEM_HOST or TZ_MEM_DEVICE");
   const double *dA = A_true, *dB = B_true, *dnoise = noise;
@@ -843,32 +857,23 @@ int tz_simulate_batch(tz_problem* p, int32_t B, int32_t T, const double* x0, con
     TZ_HIP(p->xtraj.alloc((size_t)B * (T + 1) * n)); TZ_HIP(p->utraj.alloc((size_t)B * T * m));
     TZ_HIP(p->costtraj.alloc((size_t)B * T));
     dA = p->plantA.p; dB = p->plantB.p; dnoise = p->noise.p; dx = p->xtraj.p; du = p->utraj.p; dcost = p->costtraj.p;
-    TZ_HIP(hipMemcpy2DAsync(dx, (size_t)(T + 1) * n * sizeof(double), x0, (size_t)n * sizeof(double), (size_t)n * sizeof(double), B, hipMemcpyHostToDevice, st));
-    TZ_HIP(hipMemcpyAsync(p->st_x.p, x0, (size_t)B * n * sizeof(double), hipMemcpyHostToDevice, st));
-  } else {
-    if (!cost) { TZ_HIP(p->costtraj.alloc((size_t)B * T)); dcost = p->costtraj.p; }
-    TZ_HIP(hipMemcpy2DAsync(dx, (size_t)(T + 1) * n * sizeof(double), x0, (size_t)n * sizeof(double), (size_t)n * sizeof(double), B, hipMemcpyDeviceToDevice, st));
-    TZ_HIP(hipMemcpyAsync(p->st_x.p, x0, (size_t)B * n * sizeof(double), hipMemcpyDeviceToDevice, st));
+  } else if (!cost) {
+    TZ_HIP(p->costtraj.alloc((size_t)B * T)); dcost = p->costtraj.p;
   }
+  const hipMemcpyKind in = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+  TZ_HIP(hipMemcpy2DAsync(dx, (size_t)(T + 1) * n * sizeof(double), x0, (size_t)n * sizeof(double), (size_t)n * sizeof(double), B, in, st));
+  TZ_HIP(hipMemcpyAsync(p->st_x.p, x0, (size_t)B * n * sizeof(double), in, st));
   TZ_HIP(hipMemcpyAsync(p->st_xbar.p, p->st_x.p, (size_t)B * n * sizeof(double), hipMemcpyDeviceToDevice, st));   // xbar = x0 (:69)
   TZ_HIP(hipMemsetAsync(p->st_e.p, 0, (size_t)B * n * sizeof(double), st));                                        // e = 0   (:70)
   TZ_HIP(hipMemsetAsync(p->sticky.p, 0, (size_t)B * sizeof(int), st));
-  bool warm0 = false;                                                     // a fresh loop: the stored start if there is one, else cold
-  if ((rc = closed_loop_warm(p, B, &warm0))) return rc;
-  if (p->fuse_enabled) {
-    rc = launch_step_fused(p, B, p->st_x.p, p->st_xbar.p, p->st_e.p, dnoise, (size_t)T * n, dA, dB,
-                           du, (size_t)T * m, dx + n, (size_t)(T + 1) * n,
-                           dcost, (size_t)T, p->status.p, p->sticky.p, warm0, T, StepStrides{(size_t)n, (size_t)m, (size_t)n, 1});
-    if (rc) return rc;
-  }
-  for (int t = 0; t < T && !p->fuse_enabled; ++t) {
-    rc = launch_solve(p, B, p->st_xbar.p, p->st_e.p, p->v.p, p->xbar.p, dcost + t, p->status.p, p->iters.p, nullptr, (size_t)T, t > 0 || warm0, true);
-    if (rc) return rc;
-    rc = launch_plant(p, B, dA, dB, dnoise + (size_t)t * n, (size_t)T * n, p->v.p, p->xbar.p, p->status.p,
-                      p->st_x.p, p->st_xbar.p, p->st_e.p, du + (size_t)t * m, (size_t)T * m,
-                      dx + (size_t)(t + 1) * n, (size_t)(T + 1) * n, p->sticky.p);
-    if (rc) return rc;
-  }
+  ClosedLoopIO io{};
+  io.x = p->st_x.p; io.xbar = p->st_xbar.p; io.e = p->st_e.p; io.A = dA; io.Bm = dB;
+  io.w = dnoise; io.w_stride = (size_t)T * n; io.w_step = (size_t)n;
+  io.u_out = du; io.u_stride = (size_t)T * m; io.u_step = (size_t)m;
+  io.x_out = dx + n; io.x_stride = (size_t)(T + 1) * n; io.x_step = (size_t)n;
+  io.cost = dcost; io.cost_stride = (size_t)T; io.cost_step = 1;                         // a cost per step
+  io.status = p->status.p; io.sticky = p->sticky.p; io.fresh = true;                     // the stored start if there is one, else cold
+  if (int rc = run_closed_loop(p, B, T, io)) return rc;
   if (host) {
     TZ_HIP(hipMemcpyAsync(x_traj, dx, (size_t)B * (T + 1) * n * sizeof(double), hipMemcpyDeviceToHost, st));
     TZ_HIP(hipMemcpyAsync(u_traj, du, (size_t)B * T * m * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -912,7 +917,7 @@ int tz_problem_set_warm_push(tz_problem* p, double floor, double gain, double ca
 
 int tz_problem_reset_warm(tz_problem* p) {
   if (!p) TZ_FAIL(TZ_ERR_INVALID, "null problem");
-  p->have_prev = false;
+  p->warm.invalidate();
   if (p->Bcap > 0) {
     TZ_HIP(hipSetDevice(p->device));
     TZ_HIP(hipMemsetAsync(p->shift_state.p, 0, (size_t)p->Bcap * sizeof(int), p->stream));
