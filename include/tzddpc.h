@@ -21,13 +21,14 @@
 #ifndef TZDDPC_H
 #define TZDDPC_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
 extern "C" {
 #endif
 
-#define TZ_ABI_VERSION 5
+#define TZ_ABI_VERSION 6
 
 typedef enum tz_status {
   TZ_OK = 0,
@@ -276,6 +277,46 @@ int tz_mpc_step(tz_problem* p, int32_t B, double* x, double* xbar, double* e, co
  * the values of the last step; status is the sticky first non-zero status.  Same results as K calls of tz_mpc_step. */
 int tz_mpc_run(tz_problem* p, int32_t B, int32_t K, double* x, double* xbar, double* e, const double* w,
                const double* A_true, const double* B_true, double* u_out, double* cost, int32_t* status);
+
+/*
+ * The three closed-loop entry points with ONE PLANT PER TRAJECTORY: A_true is B x n x n, B_true B x n x m, trajectory b runs on
+ * x+ = A_b x + B_b u + w (examples/1.double_integrator_sim.py:85 with its own A, B); everything else -- arguments, warm start,
+ * stored start, shift policy, status -- as in the call without the suffix.  What they are for: the closed loop on the OTHER models
+ * that explain the data, i.e. plants drawn from Mdata (tz_sample_plants), thousands at once; the reference samples Mdata only
+ * for the gain (tzddpc/utils.py:105-129).  B copies of one plant give the results of the shared-plant call bit for bit.
+ */
+int tz_simulate_batch_plants(tz_problem* p, int32_t B, int32_t T, const double* x0, const double* noise,
+                             const double* A_true, const double* B_true,
+                             double* x_traj, double* u_traj, double* cost, int32_t* status, int mem);
+int tz_mpc_step_plants(tz_problem* p, int32_t B, double* x, double* xbar, double* e, const double* w,
+                       const double* A_true, const double* B_true, double* u_out, double* cost, int32_t* status);
+int tz_mpc_run_plants(tz_problem* p, int32_t B, int32_t K, double* x, double* xbar, double* e, const double* w,
+                      const double* A_true, const double* B_true, double* u_out, double* cost, int32_t* status);
+
+/*
+ * Points of a (matrix) zonotope drawn on the device, one per trajectory (and step): centre + sum_i beta_i gen_i, the sampling idea of
+ * reference tzddpc/utils.py:105-129 (Mdata.sample()) with a counter-based generator, so that the value of global trajectory
+ * i = first + b does not depend on how a batch is cut into calls or ranks.  Blocking; centre and gen are HOST pointers, `mem`
+ * describes the outputs.  Argument errors are reported before any device query.
+ *
+ * Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85), key (seed & 0xffffffff, seed >> 32),
+ * counter (i & 0xffffffff, i >> 32, t, stream * 2^24 + j): t the step (0 for plants), stream 0 plants / 1 noise, j the block index.
+ *   TZ_SAMPLE_UNIFORM  block j gives beta_{2j} from output words (w0, w1) and beta_{2j+1} from (w2, w3):
+ *                      k = (wa >> 5) * 2^26 + (wb >> 6), beta = k * 2^-52 - 1   in [-1, 1), exact in double precision
+ *   TZ_SAMPLE_VERTEX   block j gives beta_{128j} .. beta_{128j+127}: coefficient i is bit (i mod 32) of word (i mod 128) / 32,
+ *                      set -> +1, clear -> -1
+ * The sum runs over the generators in increasing i (fused multiply-adds or not is the compiler's choice).  ngen <= 2^24.
+ * tzddpc_amd/montecarlo.py states the same stream in numpy.
+ */
+enum { TZ_SAMPLE_UNIFORM = 0, TZ_SAMPLE_VERTEX = 1 };
+/* plant b = centre + sum_i beta_i gen_i, split into A_out (B x n x n) and B_out (B x n x m); centre: n x (n+m), gen: ngen x n x (n+m) */
+int tz_sample_plants(int device, uint64_t seed, int64_t first, int32_t B, int32_t n, int32_t m, int32_t ngen,
+                     const double* centre, const double* gen, int32_t mode, double* A_out, double* B_out, int mem);
+/* w(b, t) = centre + sum_i beta_i gen_i, written to out[b * traj_stride + t * step_stride + 0..n-1]; centre: n, gen: ngen x n.
+ * (traj_stride, step_stride) = (T n, n) is the B x T x n table of tz_simulate_batch, (n, B n) the step-major one of tz_mpc_run. */
+int tz_sample_noise(int device, uint64_t seed, int64_t first, int32_t B, int32_t T, int32_t n, int32_t ngen,
+                    const double* centre, const double* gen, int32_t mode, size_t traj_stride, size_t step_stride,
+                    double* out, int mem);
 
 /* Stored start.  Solves the problem once, cold, for the parameters (xbar0, e0) (host pointers, n doubles each; typically the centre of
  * X0 and e0 = 0: where every closed loop of the reference's examples begins, examples/1.double_integrator_sim.py:62-70) and keeps

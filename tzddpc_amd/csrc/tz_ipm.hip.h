@@ -892,8 +892,11 @@ __global__ __launch_bounds__(TZ_THREADS, MINW) void tz_ipm_kernel(IpmParams p) {
     for (int i = t; i < n2; i += TZ_THREADS) tbl[i] = (i < n1) ? F0.tube.CKpow[i] : F0.tube.T[i - n1];
     // constants of the recovery / plant update: [A | B | K | r1 | R2 | Phi rows of xbar[1] | Gam rows of xbar[1] | Dz(v)]
     double* ec = tbl + n2;
-    for (int i = t; i < n * n; i += TZ_THREADS) { ec[i] = F0.plant.A[i]; ec[2 * n * m + n * n + n + i] = F0.fin.R2[i]; ec[2 * n * m + 2 * n * n + n + i] = F0.fin.Phi[(size_t)n * n + i]; }
-    for (int i = t; i < n * m; i += TZ_THREADS) { ec[n * n + i] = F0.plant.Bm[i]; ec[n * n + n * m + i] = F0.plant.K[i]; }
+    // the plant of this trajectory: the batch's (stride 0) or its own; b is the workgroup index, so the offsets are scalar work
+    const double* plA = F0.plant.A + (size_t)b * F0.plant.A_stride;
+    const double* plB = F0.plant.Bm + (size_t)b * F0.plant.B_stride;
+    for (int i = t; i < n * n; i += TZ_THREADS) { ec[i] = plA[i]; ec[2 * n * m + n * n + n + i] = F0.fin.R2[i]; ec[2 * n * m + 2 * n * n + n + i] = F0.fin.Phi[(size_t)n * n + i]; }
+    for (int i = t; i < n * m; i += TZ_THREADS) { ec[n * n + i] = plB[i]; ec[n * n + n * m + i] = F0.plant.K[i]; }
     for (int i = t; i < n; i += TZ_THREADS) ec[n * n + 2 * n * m + i] = F0.fin.r1[i];
     for (int i = t; i < n * nv; i += TZ_THREADS) ec[3 * n * n + 2 * n * m + n + i] = F0.fin.Gam[(size_t)n * nv + i];
     for (int i = t; i < nv; i += TZ_THREADS) ec[3 * n * n + 2 * n * m + n + n * nv + i] = F0.fin.Dz[i];

@@ -177,6 +177,7 @@ struct FinishParams {
 struct PlantParams {
   int B, n, m, N;
   const double* K; const double* A; const double* Bm;
+  size_t A_stride, B_stride;                  // elements between the plants of two trajectories (n n, n m); 0: one plant for the batch
   const double* v; const double* xbar_pred;   // B x N x m, B x (N+1) x n
   const double* w;                            // B x n  (stride w_stride between trajectories)
   size_t w_stride;
@@ -271,12 +272,15 @@ __global__ __launch_bounds__(64) void tz_finish_kernel(FinishParams p) {
 // ------------------------------------------------------------------------------------------------
 // Plant / error update: one thread per trajectory.
 //   u = K e + v0 ; x+ = A x + B u + w ; xbar+ = xbar[1] ; e+ = x+ - xbar+
+// A, B: the plant of the batch, or of this trajectory (A_stride / B_stride != 0: a sampled model of Mdata per closed loop).
 // ------------------------------------------------------------------------------------------------
 __global__ void tz_plant_kernel(PlantParams p) {
   int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= p.B) return;
   const int n = p.n, m = p.m;
   double x[TZ_NMAX], e[TZ_NMAX], u[TZ_MMAX], xn[TZ_NMAX];
+  const double* A = p.A + (size_t)b * p.A_stride;
+  const double* Bm = p.Bm + (size_t)b * p.B_stride;
   const int st = p.status[b];
   if (p.sticky && p.sticky[b] == 0 && st != 0) p.sticky[b] = st;
   for (int i = 0; i < n; ++i) { x[i] = p.x[(size_t)b * n + i]; e[i] = p.e[(size_t)b * n + i]; }
@@ -288,8 +292,8 @@ __global__ void tz_plant_kernel(PlantParams p) {
   }
   for (int i = 0; i < n; ++i) {
     double a = p.w[(size_t)b * p.w_stride + i];
-    for (int j = 0; j < n; ++j) a += p.A[i * n + j] * x[j];
-    for (int j = 0; j < m; ++j) a += p.Bm[i * m + j] * u[j];
+    for (int j = 0; j < n; ++j) a += A[i * n + j] * x[j];
+    for (int j = 0; j < m; ++j) a += Bm[i * m + j] * u[j];
     xn[i] = a;
   }
   for (int i = 0; i < n; ++i) {

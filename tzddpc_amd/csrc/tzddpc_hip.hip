@@ -3,6 +3,7 @@
 // launches the kernels of tz_kernels.hip.h on one HIP stream.  No torch types, no CPU compute fallback: every
 // numeric result comes out of a kernel.
 #include "tz_kernels.hip.h"
+#include "tz_sample.hip.h"
 #include "tz_plan.h"
 
 // Neither build of the library reads an environment variable: what a caller may choose goes through tz_problem_desc (plan_flags)
@@ -370,7 +371,8 @@ FinishParams finish_params(const tz_problem* p, int B) {
 struct ClosedLoopIO {
   double* x; double* xbar; double* e;                  // B x n each: the state, advanced in place
   const double* w; size_t w_stride, w_step;            // disturbances
-  const double* A; const double* Bm;                   // the true plant
+  const double* A; const double* Bm;                   // the plant: n x n, n x m ...
+  size_t A_stride, B_stride;                           // ... of the batch (0), or one per trajectory (n n, n m: the *_plants entry points)
   double* u_out; size_t u_stride, u_step;              // may be null
   double* x_out; size_t x_stride, x_step;              // may be null: copy of x+
   double* cost; size_t cost_stride, cost_step;         // cost_step 0: one slot per trajectory, overwritten by every step
@@ -382,7 +384,7 @@ struct ClosedLoopIO {
 
 PlantParams plant_params(const tz_problem* p, int B, const ClosedLoopIO& io) {        // step 0; v and xbar_pred stay null (fused step)
   PlantParams q{};
-  q.B = B; q.n = p->n; q.m = p->m; q.N = p->N; q.K = p->K.p; q.A = io.A; q.Bm = io.Bm;
+  q.B = B; q.n = p->n; q.m = p->m; q.N = p->N; q.K = p->K.p; q.A = io.A; q.Bm = io.Bm; q.A_stride = io.A_stride; q.B_stride = io.B_stride;
   q.w = io.w; q.w_stride = io.w_stride; q.status = io.status; q.x = io.x; q.xbar = io.xbar; q.e = io.e;
   q.u_out = io.u_out; q.u_stride = io.u_stride; q.x_out = io.x_out; q.x_stride = io.x_stride; q.sticky = io.sticky;
   return q;
@@ -574,6 +576,75 @@ int tz_specrad_batch(int device, int32_t S, int32_t n, int32_t ngen, const doubl
 int tz_adversary_batch(int device, int32_t S, int32_t n, int32_t ngen, const double* M0, const double* H, const double* beta0,
                        int32_t max_iter, double* beta, double* fro, int32_t* steps) {
   return gain_batch(true, device, S, n, ngen, M0, H, beta0, max_iter, beta, fro, steps);
+}
+
+// ---- Monte Carlo over the model set (tz_sample.hip.h): plants of Mdata and disturbances of W, drawn on the device --------------
+// The checks both entry points share; before the device query, so a machine without a GPU reports a bad call as such.
+static int sample_check(int32_t B, int32_t ngen, const double* centre, const double* gen, int32_t mode, int64_t first, int mem) {
+  if (!centre || (ngen > 0 && !gen)) TZ_FAIL(TZ_ERR_INVALID, "null argument");
+  if (B <= 0 || ngen < 0 || first < 0) TZ_FAIL(TZ_ERR_INVALID, "B must be positive, ngen and first non-negative");
+  if (ngen > TZ_SP_MAXGEN) TZ_FAIL(TZ_ERR_INVALID, "at most %d generators (24 bits of the counter carry the block index)", TZ_SP_MAXGEN);
+  if (mode != TZ_SAMPLE_UNIFORM && mode != TZ_SAMPLE_VERTEX) TZ_FAIL(TZ_ERR_INVALID, "mode must be TZ_SAMPLE_UNIFORM or TZ_SAMPLE_VERTEX");
+  if (mem != TZ_MEM_HOST && mem != TZ_MEM_DEVICE) TZ_FAIL(TZ_ERR_INVALID, "mem must be TZ_MEM_HOST or TZ_MEM_DEVICE");
+  return TZ_OK;
+}
+
+// uploads centre and generators, fills the fields every launch shares, launches; q carries the item shape and the outputs
+static int sample_launch(SampleParams q, uint64_t seed, int64_t first, const double* centre, const double* gen, int32_t mode,
+                         DevBuf<double>& dc, DevBuf<double>& dg) {
+  TZ_HIP(dc.upload(centre, (size_t)q.nout));
+  if (q.ngen > 0) TZ_HIP(dg.upload(gen, (size_t)q.ngen * q.nout));
+  q.key0 = (unsigned)(seed & 0xffffffffu); q.key1 = (unsigned)(seed >> 32); q.first = (unsigned long long)first;
+  q.mode = mode == TZ_SAMPLE_VERTEX ? TZ_SP_VERTEX : TZ_SP_UNIFORM; q.centre = dc.p; q.gen = dg.p;
+  const unsigned long long items = (unsigned long long)q.B * q.T;
+  hipLaunchKernelGGL(tz_sample_kernel, dim3((unsigned)((items + TZ_SP_ITEMS - 1) / TZ_SP_ITEMS)), dim3(64 * TZ_SP_ITEMS), 0, 0, q);
+  TZ_HIP(hipGetLastError());
+  return TZ_OK;
+}
+
+int tz_sample_plants(int device, uint64_t seed, int64_t first, int32_t B, int32_t n, int32_t m, int32_t ngen,
+                     const double* centre, const double* gen, int32_t mode, double* A_out, double* B_out, int mem) {
+  if (!A_out || !B_out) TZ_FAIL(TZ_ERR_INVALID, "null argument");
+  if (int rc = sample_check(B, ngen, centre, gen, mode, first, mem)) return rc;
+  if (n < 1 || n > TZ_NMAX || m < 1 || m > TZ_MMAX) TZ_FAIL(TZ_ERR_INVALID, "dim_x must be 1..%d and dim_u 1..%d", TZ_NMAX, TZ_MMAX);
+  if (int rc = use_device(device)) return rc;
+  const size_t b = (size_t)B, nn = (size_t)n * n, nm = (size_t)n * m;
+  DevBuf<double> dc, dg, dA, dB;
+  SampleParams q{};
+  q.B = B; q.T = 1; q.nout = n * (n + m); q.ngen = ngen; q.stream = 0; q.width = n + m; q.wA = n;
+  q.out0 = A_out; q.s0 = nn; q.out1 = B_out; q.s1 = nm;
+  if (mem == TZ_MEM_HOST) { TZ_HIP(dA.alloc(b * nn)); TZ_HIP(dB.alloc(b * nm)); q.out0 = dA.p; q.out1 = dB.p; }
+  if (int rc = sample_launch(q, seed, first, centre, gen, mode, dc, dg)) return rc;
+  if (mem == TZ_MEM_HOST) {
+    TZ_HIP(hipMemcpy(A_out, dA.p, b * nn * sizeof(double), hipMemcpyDeviceToHost));
+    TZ_HIP(hipMemcpy(B_out, dB.p, b * nm * sizeof(double), hipMemcpyDeviceToHost));
+  } else TZ_HIP(hipDeviceSynchronize());          // centre / gen copies are freed on return
+  return TZ_OK;
+}
+
+int tz_sample_noise(int device, uint64_t seed, int64_t first, int32_t B, int32_t T, int32_t n, int32_t ngen,
+                    const double* centre, const double* gen, int32_t mode, size_t traj_stride, size_t step_stride,
+                    double* out, int mem) {
+  if (!out) TZ_FAIL(TZ_ERR_INVALID, "null argument");
+  if (int rc = sample_check(B, ngen, centre, gen, mode, first, mem)) return rc;
+  if (T <= 0) TZ_FAIL(TZ_ERR_INVALID, "T must be positive");
+  if (n < 1 || n > TZ_NMAX) TZ_FAIL(TZ_ERR_INVALID, "dim_x must be 1..%d", TZ_NMAX);
+  if ((unsigned long long)B * T > 0x7fffffffull) TZ_FAIL(TZ_ERR_INVALID, "B * T must stay below 2^31");
+  // the two layouts that do not overlap: trajectory-major (B x T x n and wider) or step-major (T x B x n and wider)
+  const bool traj_major = step_stride >= (size_t)n && traj_stride >= (size_t)T * step_stride;
+  const bool step_major = traj_stride >= (size_t)n && step_stride >= (size_t)B * traj_stride;
+  if (!traj_major && !step_major) TZ_FAIL(TZ_ERR_INVALID, "traj_stride / step_stride describe overlapping rows");
+  if (int rc = use_device(device)) return rc;
+  const size_t extent = (size_t)(B - 1) * traj_stride + (size_t)(T - 1) * step_stride + n;
+  DevBuf<double> dc, dg, dout;
+  SampleParams q{};
+  q.B = B; q.T = T; q.nout = n; q.ngen = ngen; q.stream = 1; q.width = 0;
+  q.out0 = out; q.s0 = traj_stride; q.st0 = step_stride;
+  if (mem == TZ_MEM_HOST) { TZ_HIP(dout.upload(out, extent)); q.out0 = dout.p; }      // what lies between the rows is handed back as it came
+  if (int rc = sample_launch(q, seed, first, centre, gen, mode, dc, dg)) return rc;
+  if (mem == TZ_MEM_HOST) TZ_HIP(hipMemcpy(out, dout.p, extent * sizeof(double), hipMemcpyDeviceToHost));
+  else TZ_HIP(hipDeviceSynchronize());
+  return TZ_OK;
 }
 
 int tz_genstack_create(int device, const tz_genstack_desc* d, tz_genstack** out) {
@@ -812,35 +883,41 @@ int tz_problem_store_start(tz_problem* p, const double* xbar0, const double* e0)
   return TZ_OK;
 }
 
-int tz_mpc_step(tz_problem* p, int32_t B, double* x, double* xbar, double* e, const double* w,
-                const double* A_true, const double* B_true, double* u_out, double* cost, int32_t* status) {
+// The closed-loop entry points and their *_plants forms (per_traj: A_true is B x n x n, B_true B x n x m) differ in the plant strides only.
+static void set_plant(const tz_problem* p, ClosedLoopIO& io, const double* A, const double* Bm, bool per_traj) {
+  io.A = A; io.Bm = Bm;
+  io.A_stride = per_traj ? (size_t)p->n * p->n : 0; io.B_stride = per_traj ? (size_t)p->n * p->m : 0;
+}
+
+static int mpc_step(tz_problem* p, int32_t B, double* x, double* xbar, double* e, const double* w,
+                    const double* A_true, const double* B_true, bool per_traj, double* u_out, double* cost, int32_t* status) {
   if (!p || !x || !xbar || !e || !w || !A_true || !B_true || !cost || !status) TZ_FAIL(TZ_ERR_INVALID, "null argument");
   if (B <= 0) TZ_FAIL(TZ_ERR_INVALID, "batch size must be positive");
   TZ_HIP(hipSetDevice(p->device));
   if (int rc = ensure_workspace(p, B)) return rc;
   ClosedLoopIO io{};
-  io.x = x; io.xbar = xbar; io.e = e; io.w = w; io.w_stride = (size_t)p->n; io.A = A_true; io.Bm = B_true;
+  io.x = x; io.xbar = xbar; io.e = e; io.w = w; io.w_stride = (size_t)p->n; set_plant(p, io, A_true, B_true, per_traj);
   io.u_out = u_out; io.u_stride = (size_t)p->m; io.cost = cost; io.cost_stride = 1;
   io.status = status;                       // the solver status itself; no sticky record
   return run_closed_loop(p, B, 1, io);
 }
 
-int tz_mpc_run(tz_problem* p, int32_t B, int32_t K, double* x, double* xbar, double* e, const double* w,
-               const double* A_true, const double* B_true, double* u_out, double* cost, int32_t* status) {
+static int mpc_run(tz_problem* p, int32_t B, int32_t K, double* x, double* xbar, double* e, const double* w,
+                   const double* A_true, const double* B_true, bool per_traj, double* u_out, double* cost, int32_t* status) {
   if (!p || !x || !xbar || !e || !w || !A_true || !B_true || !cost || !status) TZ_FAIL(TZ_ERR_INVALID, "null argument");
   if (B <= 0 || K <= 0) TZ_FAIL(TZ_ERR_INVALID, "B and K must be positive");
   TZ_HIP(hipSetDevice(p->device));
   if (int rc = ensure_workspace(p, B)) return rc;
   ClosedLoopIO io{};
-  io.x = x; io.xbar = xbar; io.e = e; io.w = w; io.w_stride = (size_t)p->n; io.w_step = (size_t)B * p->n; io.A = A_true; io.Bm = B_true;
+  io.x = x; io.xbar = xbar; io.e = e; io.w = w; io.w_stride = (size_t)p->n; io.w_step = (size_t)B * p->n; set_plant(p, io, A_true, B_true, per_traj);
   io.u_out = u_out; io.u_stride = (size_t)p->m; io.cost = cost; io.cost_stride = 1;      // u and cost of the last step survive
   io.status = p->status.p; io.sticky = status; io.sticky_fresh = true;                   // the caller sees the first failure of the run
   return run_closed_loop(p, B, K, io);
 }
 
-int tz_simulate_batch(tz_problem* p, int32_t B, int32_t T, const double* x0, const double* noise,
-                      const double* A_true, const double* B_true, double* x_traj, double* u_traj,
-                      double* cost, int32_t* status, int mem) {
+static int simulate_batch(tz_problem* p, int32_t B, int32_t T, const double* x0, const double* noise,
+                          const double* A_true, const double* B_true, bool per_traj, double* x_traj, double* u_traj,
+                          double* cost, int32_t* status, int mem) {
   if (!p || !x0 || !noise || !A_true || !B_true || !x_traj || !u_traj || !status) TZ_FAIL(TZ_ERR_INVALID, "null argument");
   if (B <= 0 || T <= 0) TZ_FAIL(TZ_ERR_INVALID, "B and T must be positive");
   TZ_HIP(hipSetDevice(p->device));
@@ -852,7 +929,8 @@ int tz_simulate_batch(tz_problem* p, int32_t B, int32_t T, const double* x0, con
   const double *dA = A_true, *dB = B_true, *dnoise = noise;
   double *dx = x_traj, *du = u_traj, *dcost = cost;
   if (host) {
-    TZ_HIP(p->plantA.upload(A_true, (size_t)n * n)); TZ_HIP(p->plantB.upload(B_true, (size_t)n * m));
+    const size_t np = per_traj ? (size_t)B : 1;
+    TZ_HIP(p->plantA.upload(A_true, np * n * n)); TZ_HIP(p->plantB.upload(B_true, np * n * m));
     TZ_HIP(p->noise.upload(noise, (size_t)B * T * n));
     TZ_HIP(p->xtraj.alloc((size_t)B * (T + 1) * n)); TZ_HIP(p->utraj.alloc((size_t)B * T * m));
     TZ_HIP(p->costtraj.alloc((size_t)B * T));
@@ -867,7 +945,7 @@ int tz_simulate_batch(tz_problem* p, int32_t B, int32_t T, const double* x0, con
   TZ_HIP(hipMemsetAsync(p->st_e.p, 0, (size_t)B * n * sizeof(double), st));                                        // e = 0   (:70)
   TZ_HIP(hipMemsetAsync(p->sticky.p, 0, (size_t)B * sizeof(int), st));
   ClosedLoopIO io{};
-  io.x = p->st_x.p; io.xbar = p->st_xbar.p; io.e = p->st_e.p; io.A = dA; io.Bm = dB;
+  io.x = p->st_x.p; io.xbar = p->st_xbar.p; io.e = p->st_e.p; set_plant(p, io, dA, dB, per_traj);
   io.w = dnoise; io.w_stride = (size_t)T * n; io.w_step = (size_t)n;
   io.u_out = du; io.u_stride = (size_t)T * m; io.u_step = (size_t)m;
   io.x_out = dx + n; io.x_stride = (size_t)(T + 1) * n; io.x_step = (size_t)n;
@@ -884,6 +962,35 @@ int tz_simulate_batch(tz_problem* p, int32_t B, int32_t T, const double* x0, con
     TZ_HIP(hipMemcpyAsync(status, p->sticky.p, (size_t)B * sizeof(int), hipMemcpyDeviceToDevice, st));
   }
   return TZ_OK;
+}
+
+int tz_mpc_step(tz_problem* p, int32_t B, double* x, double* xbar, double* e, const double* w,
+                const double* A_true, const double* B_true, double* u_out, double* cost, int32_t* status) {
+  return mpc_step(p, B, x, xbar, e, w, A_true, B_true, false, u_out, cost, status);
+}
+int tz_mpc_step_plants(tz_problem* p, int32_t B, double* x, double* xbar, double* e, const double* w,
+                       const double* A_true, const double* B_true, double* u_out, double* cost, int32_t* status) {
+  return mpc_step(p, B, x, xbar, e, w, A_true, B_true, true, u_out, cost, status);
+}
+
+int tz_mpc_run(tz_problem* p, int32_t B, int32_t K, double* x, double* xbar, double* e, const double* w,
+               const double* A_true, const double* B_true, double* u_out, double* cost, int32_t* status) {
+  return mpc_run(p, B, K, x, xbar, e, w, A_true, B_true, false, u_out, cost, status);
+}
+int tz_mpc_run_plants(tz_problem* p, int32_t B, int32_t K, double* x, double* xbar, double* e, const double* w,
+                      const double* A_true, const double* B_true, double* u_out, double* cost, int32_t* status) {
+  return mpc_run(p, B, K, x, xbar, e, w, A_true, B_true, true, u_out, cost, status);
+}
+
+int tz_simulate_batch(tz_problem* p, int32_t B, int32_t T, const double* x0, const double* noise,
+                      const double* A_true, const double* B_true, double* x_traj, double* u_traj,
+                      double* cost, int32_t* status, int mem) {
+  return simulate_batch(p, B, T, x0, noise, A_true, B_true, false, x_traj, u_traj, cost, status, mem);
+}
+int tz_simulate_batch_plants(tz_problem* p, int32_t B, int32_t T, const double* x0, const double* noise,
+                             const double* A_true, const double* B_true, double* x_traj, double* u_traj,
+                             double* cost, int32_t* status, int mem) {
+  return simulate_batch(p, B, T, x0, noise, A_true, B_true, true, x_traj, u_traj, cost, status, mem);
 }
 
 int tz_problem_set_warm_shift(tz_problem* p, int32_t policy) {

@@ -11,9 +11,11 @@ from typing import Optional
 
 import numpy as np
 
-TZ_ABI_VERSION = 5
+TZ_ABI_VERSION = 6
 TZ_MEM_HOST, TZ_MEM_DEVICE = 0, 1
 TZ_SOLVED, TZ_MAX_ITER, TZ_NUMERICAL, TZ_INFEASIBLE = 0, 1, 2, 3
+TZ_ERR_INVALID, TZ_ERR_HIP, TZ_ERR_UNSUPPORTED = -1, -2, -3
+TZ_SAMPLE_UNIFORM, TZ_SAMPLE_VERTEX = 0, 1
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libtzddpc_hip_prof.so" if os.environ.get("TZ_PROF") == "1" else "libtzddpc_hip.so")
@@ -95,6 +97,11 @@ def lib():
     L.tz_simulate_batch.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int]
     L.tz_mpc_step.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.tz_mpc_run.argtypes = [vp, C.c_int32, C.c_int32] + [vp] * 9
+    L.tz_simulate_batch_plants.argtypes = L.tz_simulate_batch.argtypes          # the plants are B x n x n, B x n x m there
+    L.tz_mpc_step_plants.argtypes = L.tz_mpc_step.argtypes
+    L.tz_mpc_run_plants.argtypes = L.tz_mpc_run.argtypes
+    L.tz_sample_plants.argtypes = [C.c_int, C.c_uint64, C.c_int64] + [C.c_int32] * 4 + [vp, vp, C.c_int32, vp, vp, C.c_int]
+    L.tz_sample_noise.argtypes = [C.c_int, C.c_uint64, C.c_int64] + [C.c_int32] * 4 + [vp, vp, C.c_int32, C.c_size_t, C.c_size_t, vp, C.c_int]
     L.tz_identify_batch.argtypes = [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [vp] * 4 + [C.c_int32] + [vp] * 5 + [C.c_int]
     L.tz_identify_batch.restype = C.c_int
     L.tz_specrad_batch.argtypes = [C.c_int, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp]
@@ -129,7 +136,8 @@ def lib():
     L.tz_debug_fetch.argtypes = [vp, C.c_int32, C.c_int, vp, C.c_int32]
     for name in ("tz_device_count", "tz_problem_create", "tz_problem_destroy", "tz_problem_set_stream", "tz_problem_sync",
                  "tz_solve_batch", "tz_simulate_batch", "tz_mpc_step", "tz_mpc_run", "tz_timing_enable", "tz_timing_get",
-                 "tz_ipm_plan_info", "tz_ipm_work_get", "tz_debug_fetch", "tz_problem_reset_warm", "tz_problem_set_warm_shift"):
+                 "tz_ipm_plan_info", "tz_ipm_work_get", "tz_debug_fetch", "tz_problem_reset_warm", "tz_problem_set_warm_shift",
+                 "tz_simulate_batch_plants", "tz_mpc_step_plants", "tz_mpc_run_plants", "tz_sample_plants", "tz_sample_noise"):
         getattr(L, name).restype = C.c_int
     if L.tz_abi_version() != TZ_ABI_VERSION:
         raise NativeError(f"ABI mismatch: library {L.tz_abi_version()} vs binding {TZ_ABI_VERSION}")
@@ -141,7 +149,8 @@ EXPORTED_SYMBOLS = ("tz_abi_version", "tz_last_error", "tz_device_count", "tz_pr
                     "tz_problem_set_stream", "tz_problem_sync", "tz_solve_batch", "tz_simulate_batch", "tz_mpc_step", "tz_mpc_run",
                     "tz_timing_enable", "tz_timing_get", "tz_ipm_plan_info", "tz_ipm_work_get", "tz_debug_fetch",
                     "tz_problem_set_warm_shift", "tz_problem_set_stopping", "tz_problem_set_warm_quiet", "tz_problem_set_warm_push", "tz_problem_reset_warm", "tz_identify_batch", "tz_specrad_batch", "tz_adversary_batch",
-                    "tz_problem_attach_tube_stack", "tz_genstack_create", "tz_genstack_destroy", "tz_genstack_intervals", "tz_genstack_values", "tz_genstack_info")
+                    "tz_problem_attach_tube_stack", "tz_genstack_create", "tz_genstack_destroy", "tz_genstack_intervals", "tz_genstack_values", "tz_genstack_info",
+                    "tz_simulate_batch_plants", "tz_mpc_step_plants", "tz_mpc_run_plants", "tz_sample_plants", "tz_sample_noise")
 
 
 def check(rc: int, what: str):
@@ -205,6 +214,40 @@ def adversary_batch(device: int, M0: np.ndarray, H: np.ndarray, beta0: np.ndarra
     check(lib().tz_adversary_batch(int(device), S, n, H.shape[0], vp(M0), vp(H), vp(beta0), int(max_iter), vp(beta), vp(fro), vp(steps)),
           "tz_adversary_batch")
     return beta, fro, steps
+
+
+def _sample_mode(mode) -> int:
+    try:
+        return {"uniform": TZ_SAMPLE_UNIFORM, "vertex": TZ_SAMPLE_VERTEX}[mode]
+    except KeyError:
+        raise ValueError("mode must be 'uniform' or 'vertex'") from None
+
+
+def sample_plants(device: int, seed: int, first: int, count: int, centre: np.ndarray, gen: np.ndarray, n: int, mode="uniform"):
+    """``tz_sample_plants``: `count` plants centre + sum_i beta_i gen[i] of global trajectories first .. first + count - 1
+    (centre (n, n + m), gen (ngen, n, n + m)) -> (A (count, n, n), B (count, n, m))."""
+    centre = np.ascontiguousarray(centre, dtype=np.float64); n = int(n); m = centre.shape[1] - n
+    gen = np.ascontiguousarray(gen, dtype=np.float64).reshape((-1,) + centre.shape)
+    A = np.empty((int(count), n, n)); Bm = np.empty((int(count), n, m))
+    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+    check(lib().tz_sample_plants(int(device), int(seed), int(first), int(count), n, m, gen.shape[0], vp(centre), vp(gen),
+                                 _sample_mode(mode), vp(A), vp(Bm), TZ_MEM_HOST), "tz_sample_plants")
+    return A, Bm
+
+
+def sample_noise(device: int, seed: int, first: int, count: int, steps: int, centre: np.ndarray, gen: np.ndarray, mode="vertex",
+                 step_major: bool = False):
+    """``tz_sample_noise``: centre (n,), gen (ngen, n) -> (count, steps, n), the table of ``tz_simulate_batch``, or with
+    `step_major` (steps, count, n), the one of ``tz_mpc_run``."""
+    centre = np.ascontiguousarray(centre, dtype=np.float64).reshape(-1); n = centre.size
+    gen = np.ascontiguousarray(gen, dtype=np.float64).reshape(-1, n)
+    count, steps = int(count), int(steps)
+    out = np.empty((steps, count, n) if step_major else (count, steps, n))
+    ts, ss = (n, count * n) if step_major else (steps * n, n)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+    check(lib().tz_sample_noise(int(device), int(seed), int(first), count, steps, n, gen.shape[0], vp(centre), vp(gen),
+                                _sample_mode(mode), ts, ss, vp(out), TZ_MEM_HOST), "tz_sample_noise")
+    return out
 
 
 def _f64(a):
@@ -332,12 +375,25 @@ class Problem:
     def simulate_batch(self, x0, noise, A_true, B_true):
         x0 = _f64(x0).reshape(-1, self.n); B = x0.shape[0]
         noise = _f64(noise).reshape(B, -1, self.n); T = noise.shape[1]
-        A_true = _f64(A_true); B_true = _f64(B_true).reshape(self.n, self.m)
+        A_true, B_true, per_traj = self.plants(A_true, B_true, B)
         xt = np.empty((B, T + 1, self.n)); ut = np.empty((B, T, self.m)); cost = np.empty((B, T)); status = np.empty(B, dtype=np.int32)
         vp = lambda a: a.ctypes.data_as(C.c_void_p)
-        check(lib().tz_simulate_batch(self._h, B, T, vp(x0), vp(noise), vp(A_true), vp(B_true), vp(xt), vp(ut), vp(cost), vp(status),
-                                      TZ_MEM_HOST), "tz_simulate_batch")
+        fn, name = (lib().tz_simulate_batch_plants, "tz_simulate_batch_plants") if per_traj else (lib().tz_simulate_batch, "tz_simulate_batch")
+        check(fn(self._h, B, T, vp(x0), vp(noise), vp(A_true), vp(B_true), vp(xt), vp(ut), vp(cost), vp(status), TZ_MEM_HOST), name)
         return xt, ut, cost, status
+
+    def plants(self, A_true, B_true, B: int):
+        """A_true (n, n) or (B, n, n), B_true (n, m) or (B, n, m) -> (A, B, per_trajectory): both 2-D as they are (the shared plant);
+        if either is 3-D both come back 3-D, a 2-D one repeated for every trajectory."""
+        A_true = _f64(A_true); B_true = _f64(B_true)
+        if A_true.ndim != 3 and B_true.ndim != 3:
+            return A_true.reshape(self.n, self.n), B_true.reshape(self.n, self.m), False
+        A3 = A_true if A_true.ndim == 3 else A_true.reshape(1, self.n, self.n)
+        B3 = B_true if B_true.ndim == 3 else B_true.reshape(1, self.n, self.m)
+        if A3.shape[1:] != (self.n, self.n) or B3.shape[1:] != (self.n, self.m) or A3.shape[0] not in (1, B) or B3.shape[0] not in (1, B):
+            raise ValueError(f"plants must be ({B}, {self.n}, {self.n}) and ({B}, {self.n}, {self.m}), or one 2-D plant")
+        return (np.ascontiguousarray(np.broadcast_to(A3, (B, self.n, self.n))),
+                np.ascontiguousarray(np.broadcast_to(B3, (B, self.n, self.m))), True)
 
     # ---- device-pointer entry points (torch tensors: pass .data_ptr()) --------------------------
     def solve_batch_ptr(self, B, xbar0, e0, v, xbar, cost, status, iters=None, active=None):
@@ -348,6 +404,17 @@ class Problem:
 
     def mpc_run_ptr(self, B, K, x, xbar, e, w, A_true, B_true, u_out, cost, status):
         check(lib().tz_mpc_run(self._h, int(B), int(K), x, xbar, e, w, A_true, B_true, u_out, cost, status), "tz_mpc_run")
+
+    # one plant per trajectory: A_true (B, n, n), B_true (B, n, m)
+    def mpc_step_plants_ptr(self, B, x, xbar, e, w, A_true, B_true, u_out, cost, status):
+        check(lib().tz_mpc_step_plants(self._h, int(B), x, xbar, e, w, A_true, B_true, u_out, cost, status), "tz_mpc_step_plants")
+
+    def mpc_run_plants_ptr(self, B, K, x, xbar, e, w, A_true, B_true, u_out, cost, status):
+        check(lib().tz_mpc_run_plants(self._h, int(B), int(K), x, xbar, e, w, A_true, B_true, u_out, cost, status), "tz_mpc_run_plants")
+
+    def simulate_batch_plants_ptr(self, B, T, x0, noise, A_true, B_true, x_traj, u_traj, cost, status):
+        check(lib().tz_simulate_batch_plants(self._h, int(B), int(T), x0, noise, A_true, B_true, x_traj, u_traj, cost, status,
+                                             TZ_MEM_DEVICE), "tz_simulate_batch_plants")
 
     def simulate_batch_ptr(self, B, T, x0, noise, A_true, B_true, x_traj, u_traj, cost, status):
         check(lib().tz_simulate_batch(self._h, int(B), int(T), x0, noise, A_true, B_true, x_traj, u_traj, cost, status,

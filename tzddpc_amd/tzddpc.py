@@ -648,7 +648,9 @@ class TZDDPC(object):
         return out
 
     def simulate_batch(self, x0: np.ndarray, noise: np.ndarray, A_true: np.ndarray, B_true: np.ndarray):
-        """Closed loop of ``examples/1.double_integrator_sim.py:75-90`` for B trajectories, T = noise.shape[1] steps."""
+        """Closed loop of ``examples/1.double_integrator_sim.py:75-90`` for B trajectories, T = noise.shape[1] steps.
+        ``A_true`` (n, n) and ``B_true`` (n, m) are the plant of the whole batch; (B, n, n) / (B, n, m) give every trajectory its own
+        (``montecarlo.sample_plants``: models drawn from ``Mdata``).  One of each kind: the 2-D one is repeated."""
         if self._native is None:
             raise Exception("Problem was not built: call build_problem first")
         if getattr(self, "_cuts", None) is not None:
@@ -748,7 +750,17 @@ class TZDDPC(object):
         n, m = self.dim_x, self.dim_u
         x = np.asarray(x0, float).reshape(-1, n).copy(); Bn = x.shape[0]
         noise = np.asarray(noise, float).reshape(Bn, -1, n); T = noise.shape[1]
-        A_true = np.asarray(A_true, float); B_true = np.asarray(B_true, float).reshape(n, m)
+        A_true, B_true, per_traj = self._native.plants(A_true, B_true, Bn)
+        if not per_traj:
+            A_true, B_true = A_true[None], B_true[None]
+
+        def rows(M, z):
+            """out[b] = M[b] z[b] (M[0] for a shared plant), summed in increasing column order by elementwise operations: the same
+            bits whether a plant is handed in once or once per trajectory."""
+            acc = M[:, :, 0] * z[:, None, 0]
+            for j in range(1, z.shape[1]):
+                acc = acc + M[:, :, j] * z[:, None, j]
+            return acc
         K = np.atleast_2d(np.asarray(self.theta.K, float))
         xs = np.empty((Bn, T + 1, n)); us = np.empty((Bn, T, m)); cs = np.empty((Bn, T)); sticky = np.zeros(Bn, dtype=np.int32)
         xbar = x.copy(); e = np.zeros_like(x); xs[:, 0] = x
@@ -759,7 +771,7 @@ class TZDDPC(object):
             v0 = np.where(okb[:, None], v[:, 0], 0.0)                              # failed step: v = 0 (u = K e), nominal state follows Phi
             nxt = np.where(okb[:, None], xb[:, 1], xbar @ Phi1.T)
             u = e @ K.T + v0                                                        # :84
-            x = x @ A_true.T + u @ B_true.T + noise[:, t]                           # :85
+            x = rows(A_true, x) + rows(B_true, u) + noise[:, t]                     # :85
             xbar = nxt; e = x - xbar                                                # :83, :87
             xs[:, t + 1] = x; us[:, t] = u; cs[:, t] = np.where(okb, cost, np.inf)
             sticky = np.where((sticky == 0) & ~okb, status, sticky)
