@@ -29,35 +29,90 @@
 // iteration), and 16-byte records cost them 10 % (DI N = 80) to 14 % (5-dim, two inputs) of the kernel time (profiles/r4w_ab_r3_vs_r4.txt).
 struct TzEll { int L, VL; const TzEllEnt* ent; const int* seg; const double* val; const unsigned short* idx; };      // TzEllEnt, tz_d2, tz_ell_off: tz_kernels.hip.h
 // one virtual lane's walk over its L records, NL lanes apart.  base: wave-uniform address of record 0 of lane 0 of the pass (scalar
-// registers, advanced by scalar adds); lo: this lane's byte offset (one 32-bit vector register): no vector address arithmetic per load
+// registers, advanced by scalar adds); lo: this lane's byte offset (one 32-bit vector register): no vector address arithmetic per load.
+// The records are the same for every trajectory, step and iteration and the arithmetic is a dozen FMAs per lane: what a product
+// costs is the chain of dependent round trips to L2 for its records.  A window of TZ_ELL_D records is therefore loaded back to back
+// before its gathers and FMAs (FETCH, then APPLY), a remaining quad likewise, the L % 4 tail entries one by one; and two passes of
+// one table are walked side by side (tz_ell_walk2), each window of both in flight together.  All of it is straight-line code: the
+// forms with the records of the NEXT window requested before the current one is consumed, with uniform predication instead of the
+// three loops, or with the first window fetched ahead of the barrier that publishes the input vector were each measured slower
+// (profiles/ellfetch_headline_ab.txt).  Summation order of a pass, whatever the window: within full quads entries 0 and 2 go to a0,
+// 1 and 3 to a1, every tail entry to a0; the result is a0 + a1.
+#define TZ_ELL_D 8
 typedef __attribute__((address_space(1))) const char* tz_gptr;
 typedef __attribute__((address_space(1))) const tz_d2* tz_gd2ptr;
+// FETCH of four records at base, base + stride, ...: the four addresses as scalar base + 32-bit lane offset (the bases pinned in
+// scalar registers: the compiler otherwise folds base + lane offset into ONE 64-bit vector address and derives the other three from
+// it with vector adds); base advanced
+#define TZ_ELL_FETCH4(base, r0, r1, r2, r3) \
+  tz_d2 r0, r1, r2, r3; \
+  { tz_gptr q0 = base, q1 = base + stride, q2 = base + 2 * (size_t)stride, q3 = base + 3 * (size_t)stride; \
+    asm volatile("" : "+s"(q0), "+s"(q1), "+s"(q2), "+s"(q3)); \
+    r0 = *(tz_gd2ptr)(q0 + lo); r1 = *(tz_gd2ptr)(q1 + lo); r2 = *(tz_gd2ptr)(q2 + lo); r3 = *(tz_gd2ptr)(q3 + lo); \
+    base += 4 * (size_t)stride; }
+#define TZ_ELL_TERM(r) (r.x * *reinterpret_cast<const double*>(b + tz_ell_off(r.y)))
+#define TZ_ELL_APPLY4(a0, a1, r0, r1, r2, r3) { a0 += TZ_ELL_TERM(r0); a1 += TZ_ELL_TERM(r1); a0 += TZ_ELL_TERM(r2); a1 += TZ_ELL_TERM(r3); }
+static_assert(TZ_ELL_D == 8, "the windows of tz_ell_walk / tz_ell_walk2 are written out for eight records");
 __device__ inline double tz_ell_walk(const char* base_, unsigned lo, int L, unsigned stride, const double* in) {
   double a0 = 0.0, a1 = 0.0;
   const char* b = reinterpret_cast<const char*>(in);
   tz_gptr base = (tz_gptr)base_;
   int e = 0;
+  for (; e + TZ_ELL_D - 1 < L; e += TZ_ELL_D) {
+    TZ_ELL_FETCH4(base, r0, r1, r2, r3)
+    TZ_ELL_FETCH4(base, r4, r5, r6, r7)
+    TZ_ELL_APPLY4(a0, a1, r0, r1, r2, r3)
+    TZ_ELL_APPLY4(a0, a1, r4, r5, r6, r7)
+  }
   for (; e + 3 < L; e += 4) {
-    // the four record addresses as scalar base + 32-bit lane offset (the bases pinned in scalar registers: the compiler otherwise folds
-    // base + lane offset into ONE 64-bit vector address and derives the other three from it with vector adds)
-    tz_gptr q0 = base, q1 = base + stride, q2 = base + 2 * (size_t)stride, q3 = base + 3 * (size_t)stride;
-    asm volatile("" : "+s"(q0), "+s"(q1), "+s"(q2), "+s"(q3));
-    const tz_d2 r0 = *(tz_gd2ptr)(q0 + lo), r1 = *(tz_gd2ptr)(q1 + lo), r2 = *(tz_gd2ptr)(q2 + lo), r3 = *(tz_gd2ptr)(q3 + lo);
-    base += 4 * (size_t)stride;
-    a0 += r0.x * *reinterpret_cast<const double*>(b + tz_ell_off(r0.y));
-    a1 += r1.x * *reinterpret_cast<const double*>(b + tz_ell_off(r1.y));
-    a0 += r2.x * *reinterpret_cast<const double*>(b + tz_ell_off(r2.y));
-    a1 += r3.x * *reinterpret_cast<const double*>(b + tz_ell_off(r3.y));
+    TZ_ELL_FETCH4(base, r0, r1, r2, r3)
+    TZ_ELL_APPLY4(a0, a1, r0, r1, r2, r3)
   }
   for (; e < L; ++e) {
     tz_gptr q0 = base;
     asm volatile("" : "+s"(q0));
     const tz_d2 r = *(tz_gd2ptr)(q0 + lo);
     base += stride;
-    a0 += r.x * *reinterpret_cast<const double*>(b + tz_ell_off(r.y));
+    a0 += TZ_ELL_TERM(r);
   }
   return a0 + a1;
 }
+// two passes of one table side by side (base0_, base1_: record 0 of lane 0 of either): every window of both is in flight together,
+// each pass summed in the order of tz_ell_walk
+__device__ inline void tz_ell_walk2(const char* base0_, const char* base1_, unsigned lo, int L, unsigned stride, const double* in, double& out0, double& out1) {
+  double a0 = 0.0, a1 = 0.0, c0 = 0.0, c1 = 0.0;
+  const char* b = reinterpret_cast<const char*>(in);
+  tz_gptr base = (tz_gptr)base0_, bas2 = (tz_gptr)base1_;
+  int e = 0;
+  for (; e + TZ_ELL_D - 1 < L; e += TZ_ELL_D) {
+    TZ_ELL_FETCH4(base, r0, r1, r2, r3)
+    TZ_ELL_FETCH4(base, r4, r5, r6, r7)
+    TZ_ELL_FETCH4(bas2, s0, s1, s2, s3)
+    TZ_ELL_FETCH4(bas2, s4, s5, s6, s7)
+    TZ_ELL_APPLY4(a0, a1, r0, r1, r2, r3)
+    TZ_ELL_APPLY4(a0, a1, r4, r5, r6, r7)
+    TZ_ELL_APPLY4(c0, c1, s0, s1, s2, s3)
+    TZ_ELL_APPLY4(c0, c1, s4, s5, s6, s7)
+  }
+  for (; e + 3 < L; e += 4) {
+    TZ_ELL_FETCH4(base, r0, r1, r2, r3)
+    TZ_ELL_FETCH4(bas2, s0, s1, s2, s3)
+    TZ_ELL_APPLY4(a0, a1, r0, r1, r2, r3)
+    TZ_ELL_APPLY4(c0, c1, s0, s1, s2, s3)
+  }
+  for (; e < L; ++e) {
+    tz_gptr q0 = base, q1 = bas2;
+    asm volatile("" : "+s"(q0), "+s"(q1));
+    const tz_d2 r = *(tz_gd2ptr)(q0 + lo), s = *(tz_gd2ptr)(q1 + lo);
+    base += stride; bas2 += stride;
+    a0 += TZ_ELL_TERM(r);
+    c0 += TZ_ELL_TERM(s);
+  }
+  out0 = a0 + a1; out1 = c0 + c1;
+}
+#undef TZ_ELL_FETCH4
+#undef TZ_ELL_APPLY4
+#undef TZ_ELL_TERM
 
 // compact form: entry e of the lane at val[e * NL], idx[e * NL] (the caller offsets the pointers to the lane)
 __device__ inline double tz_ell_walk_c(const double* val, const unsigned short* idx, int L, int NL, const double* in) {
@@ -321,7 +376,16 @@ __device__ inline double tz_gemvT_get3(const double* part, int nzp, int c) {
 template <bool COMPACT>
 __device__ inline void tz_ell_gemv_walk(const IpmParams& p, const double* in, double* pl) {
   const int t = tz_tid(), L = p.eg.L;
-  for (int v0 = 0; v0 < p.eg.VL; v0 += TZ_THREADS) {
+  int v0 = 0;
+  if constexpr (!COMPACT) {
+    for (; v0 + TZ_THREADS < p.eg.VL; v0 += 2 * TZ_THREADS) {       // passes in pairs: their records in flight together
+      double s0, s1;
+      tz_ell_walk2(reinterpret_cast<const char*>(p.eg.ent + (size_t)v0 * L), reinterpret_cast<const char*>(p.eg.ent + (size_t)(v0 + TZ_THREADS) * L),
+                   (unsigned)t * 16u, L, TZ_THREADS * 16u, in, s0, s1);
+      pl[v0 + t] = s0; pl[v0 + TZ_THREADS + t] = s1;
+    }
+  }
+  for (; v0 < p.eg.VL; v0 += TZ_THREADS) {
     if constexpr (COMPACT) pl[v0 + t] = tz_ell_walk_c(p.eg.val + (size_t)v0 * L + t, p.eg.idx + (size_t)v0 * L + t, L, TZ_THREADS, in);
     else pl[v0 + t] = tz_ell_walk(reinterpret_cast<const char*>(p.eg.ent + (size_t)v0 * L), (unsigned)t * 16u, L, TZ_THREADS * 16u, in);
   }
