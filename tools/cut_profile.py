@@ -11,7 +11,7 @@ SRC = os.path.join(ROOT, "tzddpc_amd", "csrc")
 TMP = "/tmp/cutroot"
 CUTS = {
     1: ("  const bool inlaunch = fused && src == 2;\n", "after"),                                           # step top: arguments re-read, policy
-    2: ("    TZ_STAMP(PH_TUBE);\n    TZ_COLS(c, nzp) { qv[c]", "before"),                                   # + tube (both stages), shift halves
+    2: ("    TZ_STAMP(PH_TUBE);\n    // Maps of at most TZ_MAP_W4 entries per row", "before"),                # + tube (both stages), shift halves
     3: ("  if (fused && flag[1] != 0) { skip = true;", "before"),                                           # + maps, G x walk, barrier
     4: ("    TZ_STAMP(PH_WARM_B);\n", "before"),                                                            # + owner sums, violation reduction
     5: ("  // scales of the stopping test: parked in LDS", "before"),                                       # + push
@@ -30,7 +30,7 @@ ITER_CUTS = {
     10: ("    TZ_STAMP(PH_TOP);\n", "before", 1),          # quiet prefix + rejected test + weights staged
     11: ("    TZ_STAMP(PH_FORM);\n", "before", 1),         # + Gram
     12: ("    TZ_FRESH_T();\n    if constexpr (TT) TZ_TT_SOLVE(p, Hq, dinv, r1v, tmpz, dxv);", "before", 1),   # + Cholesky || right-hand side || forward substitution
-    13: ("    TZ_STAMP(PH_SOLVE);\n    tz_ell_gemv<MAXR, TT>(p, dxv, pl, rseg_, g_);\n    TZ_STAMP(PH_GEMV);\n    __builtin_amdgcn_s_setprio(TZ_PRIO_ELEM);\n    // step to the boundary", "before", 1),   # + backward substitution
+    13: ("    TZ_STAMP(PH_SOLVE);\n    tz_ell_gemv<MAXR, TT, true>(p, dxv, pl, rseg_, g_);\n    TZ_STAMP(PH_GEMV);\n    __builtin_amdgcn_s_setprio(TZ_PRIO_ELEM);\n    // step to the boundary", "before", 1),   # + backward substitution
     14: ("    __builtin_amdgcn_s_setprio(TZ_PRIO_ELEM);\n    // step to the boundary", "before", 1),              # + G dx
     15: ("    double sigma = muaff * tz_recip(mu); sigma = sigma * sigma * sigma;", "before", 1),                  # + step lengths (the predictor was not taken as the step)
     16: None,                                                                                                      # whole step with one forced iteration

@@ -402,9 +402,10 @@ __device__ inline void tz_ell_gemv_sum(const double* pl, const int (&rseg)[MAXR]
     out[k] = a;
   }
 }
-template <int MAXR, bool COMPACT>
+// SYNCED: the caller has just passed a workgroup barrier behind the last reader of pl -- the opening barrier would guard nothing
+template <int MAXR, bool COMPACT, bool SYNCED = false>
 __device__ inline void tz_ell_gemv(const IpmParams& p, const double* in, double* pl, const int (&rseg)[MAXR], double (&out)[MAXR]) {
-  __syncthreads();                                   // pl may still be read by the owners of the previous product
+  if (!SYNCED) __syncthreads();                      // pl may still be read by the owners of the previous product
   tz_ell_gemv_walk<COMPACT>(p, in, pl);
   __syncthreads();
   tz_ell_gemv_sum<MAXR>(pl, rseg, out);
@@ -1057,15 +1058,36 @@ __global__ __launch_bounds__(TZ_THREADS, MINW) void tz_ipm_kernel(IpmParams p) {
     }
     __syncthreads();
     TZ_STAMP(PH_TUBE);
-    TZ_COLS(c, nzp) { qv[c] = (c < nz) ? csr_row(F.qmap, c, thl) : 0.0; if (src != 2) xv[c] = 0.0; }
-    TZ_STAMP(PH_MAPS_Q);
-    int bad = 0;
-    for (int r = t; r < F.npar; r += TZ_THREADS) {
-      const double v = csr_row(F.parmap, r, thl);
-      if (!(v >= F.par_lo[r] - 1e-9) || !(v <= F.par_hi[r] + 1e-9)) bad = 1;
+    // Maps of at most TZ_MAP_W4 entries per row: the rows this thread owns -- column t of q, parameter row t with its bounds, row t
+    // of h -- in ONE round trip: all fetches (csr_fetch4) before the first apply.  A WAVE skips the maps of which it owns no row
+    // (one scalar branch each: the 20 to 64 columns of q and the parameter rows sit in wave 0); inside a wave that owns some, a lane
+    // without a row fetches the map's last row and drops it, so no lane mask changes between the loads.  Nothing fetched here
+    // outlives this barrier interval.  The further rows of h (r >= 256) follow one by one; wider maps and more than 256 parameter
+    // rows take csr_row throughout.
+    if (F.qmap.W <= TZ_MAP_W4 && F.hmap.W <= TZ_MAP_W4 && F.parmap.W <= TZ_MAP_W4 && F.npar <= TZ_THREADS) {
+      const int tw = __builtin_amdgcn_readfirstlane(t) & ~63;              // first thread of this wave
+      const TzMapRow4 Rh = csr_fetch4(F.hmap, min(t, mi - 1));
+      TzMapRow4 Rq = Rh, Rp = Rh; double plo = 0.0, phi = 0.0;              // (placeholders of the waves that skip the fetch: never applied)
+      if (tw < nz) Rq = csr_fetch4(F.qmap, min(t, nz - 1));
+      if (tw < F.npar) { const int rp = min(t, F.npar - 1); Rp = csr_fetch4(F.parmap, rp); plo = F.par_lo[rp]; phi = F.par_hi[rp]; }
+      TZ_COLS(c, nzp) { qv[c] = (c < nz) ? csr_apply4(F.qmap, Rq, thl) : 0.0; if (src != 2) xv[c] = 0.0; }
+      TZ_STAMP(PH_MAPS_Q);
+      if (t < F.npar) {
+        const double v = csr_apply4(F.parmap, Rp, thl);
+        if (!(v >= plo - 1e-9) || !(v <= phi + 1e-9)) flag[1] = 1;
+      }
+      TZ_ROWS(k, r) TZ_SET_H(k, r, (k == 0) ? csr_apply4(F.hmap, Rh, thl) : csr_row(F.hmap, r, thl));
+    } else {
+      TZ_COLS(c, nzp) { qv[c] = (c < nz) ? csr_row(F.qmap, c, thl) : 0.0; if (src != 2) xv[c] = 0.0; }
+      TZ_STAMP(PH_MAPS_Q);
+      int bad = 0;
+      for (int r = t; r < F.npar; r += TZ_THREADS) {
+        const double v = csr_row(F.parmap, r, thl);
+        if (!(v >= F.par_lo[r] - 1e-9) || !(v <= F.par_hi[r] + 1e-9)) bad = 1;
+      }
+      if (bad) flag[1] = 1;
+      TZ_ROWS(k, r) TZ_SET_H(k, r, csr_row(F.hmap, r, thl));
     }
-    if (bad) flag[1] = 1;
-    TZ_ROWS(k, r) TZ_SET_H(k, r, csr_row(F.hmap, r, thl));
     if (walk_early) tz_ell_gemv_walk<TT>(p, xv, pl);         // (pl: last read before the barriers above)
   } else {
     TZ_COLS(c, nzp) qv[c] = (c < nz) ? pk.q[(size_t)b * nz + c] : 0.0;
@@ -1327,9 +1349,9 @@ retry_solve:
     TZ_FRESH_T();
     if constexpr (TT) TZ_TT_SOLVE(p, Hq, dinv, r1v, tmpz, dxv);
     else tz_chol_solve_wave(p, Hq, dinv, tmpz, dxv, true);            // tmpz: y = inv(L) r1, left there by tz_fwd_trailing
-    __syncthreads();
+    __syncthreads();                                   // dx complete; the last readers of pl (column sums of G'v) are two barriers back
     TZ_STAMP(PH_SOLVE);
-    tz_ell_gemv<MAXR, TT>(p, dxv, pl, rseg_, g_);
+    tz_ell_gemv<MAXR, TT, true>(p, dxv, pl, rseg_, g_);
     TZ_STAMP(PH_GEMV);
     __builtin_amdgcn_s_setprio(TZ_PRIO_ELEM);
     // step to the boundary: alpha = 1 / max(1, max_i(-dv_i / v_i))
@@ -1362,8 +1384,7 @@ retry_solve:
       const double alphaA = (mmA > sfr) ? sfr * tz_recip(mmA) : 1.0;
       TZ_COLS(c, nz) xv[c] += alphaA * dxv[c];
       TZ_ROWS(k, r) { s_[k] += alphaA * ds_[k]; l_[k] += alphaA * dl_[k]; TZ_ADD_GX(k, r, alphaA * g_[k]); }
-      __syncthreads();
-      continue;
+      continue;                                        // no barrier: see the end of the loop body
     }
     double sigma = muaff * tz_recip(mu); sigma = sigma * sigma * sigma;
     TZ_FRESH_T();
@@ -1383,9 +1404,9 @@ retry_solve:
     TZ_STAMP(PH_GEMVT);
     if constexpr (TT) TZ_TT_SOLVE(p, Hq, dinv, r1v, tmpz, dxv);
     else tz_chol_solve_wave(p, Hq, dinv, r1v, dxv);
-    __syncthreads();
+    __syncthreads();                                   // dx complete; the last readers of pl (column sums of G'v) are two barriers back
     TZ_STAMP(PH_SOLVE);
-    tz_ell_gemv<MAXR, TT>(p, dxv, pl, rseg_, g_);
+    tz_ell_gemv<MAXR, TT, true>(p, dxv, pl, rseg_, g_);
     TZ_STAMP(PH_GEMV);
     __builtin_amdgcn_s_setprio(TZ_PRIO_ELEM);
     double ms = 0.0, ml = 0.0, z3 = 0;
@@ -1402,7 +1423,10 @@ retry_solve:
     const double alpha = (mm * 1.0 > sfr) ? sfr * tz_recip(mm) : 1.0;      // min(1, sfr * min_i(-v_i/dv_i))
     TZ_COLS(c, nz) xv[c] += alpha * dxv[c];
     TZ_ROWS(k, r) { s_[k] += alpha * ds_[k]; l_[k] += alpha * dl_[k]; TZ_ADD_GX(k, r, alpha * g_[k]); }
-    __syncthreads();
+    // No barrier here: every thread updated its own column of x and its own rows (registers, its own slots of gL).  The next reader of
+    // another thread's x is P x in exact_rd or in the predictor's right-hand side, both behind the barrier of the tz_block_reduce3 that
+    // opens the next iteration; when the loop ends here (max_iter) the status is still 1 and the retry / the certificate below begin
+    // with a barrier or a reduction before anything reads x.  dxv is written again only by the next solve, several barriers on.
   }
   __builtin_amdgcn_s_setprio(TZ_PRIO_GLUE);       // stopping test done: recovery, plant update, tube, maps and warm start of the next step are short
   TZ_FRESH_T();

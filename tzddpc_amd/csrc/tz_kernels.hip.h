@@ -127,7 +127,40 @@ struct AffineParams {
 };
 
 #define TZ_ELL_REG 8
+// A row of a map is evaluated in two halves: FETCH (c0 and the row's records, loaded back to back: one round trip to L2) and APPLY
+// (acc = c0; acc += val_e * theta[off_e] in ascending e).  A caller that owns rows of several maps issues all its fetches before the
+// first apply, so that the maps cost it one round trip together instead of one each (fused prologue of tz_ipm_kernel).
+// Maps of at most TZ_MAP_W4 entries per row (every double-integrator problem: 2 / 4 / 3 for q / h / par) take a form without a
+// branch per entry: slot e >= W re-reads record W - 1 (inside the table) and the apply leaves its term out by a uniform select, so
+// the sum is the one of the wider form bit for bit.
+#define TZ_MAP_W4 4
+struct TzMapRow4 { double c0; tz_d2 v0, v1, v2, v3; };
+__device__ inline TzMapRow4 csr_fetch4(const TzCsr& M, int r) {
+  const int W = M.W;                                   // 1 <= W <= TZ_MAP_W4 (the planner's W is at least 1)
+  const TzEllEnt* b = M.ent + r;
+  const size_t rows = (size_t)M.rows, e1 = (W > 1) ? rows : 0, e2 = (W > 2) ? 2 * rows : e1, e3 = (W > 3) ? 3 * rows : e2;
+  TzMapRow4 R;
+  R.c0 = M.c0[r];
+  R.v0 = *reinterpret_cast<const tz_d2*>(b);
+  R.v1 = *reinterpret_cast<const tz_d2*>(b + e1);
+  R.v2 = *reinterpret_cast<const tz_d2*>(b + e2);
+  R.v3 = *reinterpret_cast<const tz_d2*>(b + e3);
+  return R;
+}
+__device__ inline double csr_apply4(const TzCsr& M, const TzMapRow4& R, const double* th) {
+  const int W = M.W;
+  const char* tb = reinterpret_cast<const char*>(th);
+#define TZ_MAP_TERM(v) (v.x * *reinterpret_cast<const double*>(tb + tz_ell_off(v.y)))
+  double acc = R.c0 + TZ_MAP_TERM(R.v0);
+  const double a1 = acc + TZ_MAP_TERM(R.v1); acc = (W > 1) ? a1 : acc;
+  const double a2 = acc + TZ_MAP_TERM(R.v2); acc = (W > 2) ? a2 : acc;
+  const double a3 = acc + TZ_MAP_TERM(R.v3); acc = (W > 3) ? a3 : acc;
+#undef TZ_MAP_TERM
+  return acc;
+}
 __device__ inline double csr_row(const TzCsr& M, int r, const double* th) {
+  if (M.W <= TZ_MAP_W4) return csr_apply4(M, csr_fetch4(M, r), th);
+  // wider maps: up to TZ_ELL_REG records in registers behind one branch each, the rest one by one
   double acc = M.c0[r];
   const char* tb = reinterpret_cast<const char*>(th);
   tz_d2 v[TZ_ELL_REG];
