@@ -1247,6 +1247,20 @@ retry_solve:
     // mu already pass the test
     double nrp = 0, sl = 0, z0 = 0;
     TZ_ROWS(k, r) { rp_[k] = TZ_GX(k, r) + s_[k] - TZ_H(k, r); nrp = fmax(nrp, fabs(rp_[k])); sl += s_[k] * l_[k]; }
+    // Newton matrix.  is = 1/s, il = 1/lambda are the only two divisions per row and iteration.
+    auto stage_w = [&](bool form) {                    // form: is, il, w are not in registers yet
+      TZ_ROWS(k, r) { if (form) { is_[k] = tz_recip(s_[k]); il_[k] = tz_recip(l_[k]); w_[k] = l_[k] * is_[k]; } vin[r] = w_[k]; }
+    };
+    // The weights are staged for the Gram HERE, in front of the reduction whose barrier then publishes them, unless vin holds the
+    // lambda staged by the warm start for the test of the starting point (the last readers of vin, the G' products of the iteration
+    // before, are at least two barriers back).  Only with at most 64 variables and one row per thread.  In the class with more than 64
+    // variables an iteration whose test then passes has formed the weights for nothing, and with its two and more rows per thread
+    // that costs it what the barrier saves (5-dim problem: 0.1-0.35 % slower with it).  With more than one row per thread in the
+    // small class the longer live ranges of is / il / w raise the scratch of the 128-register instantiations (92 -> 96, 144 -> 156,
+    // 196 -> 208 B per lane), which the one-row instantiation lowers (36 -> 28).
+    const bool w_early = !TT && MAXR == 1 && !((it == 0) && warm);
+    bool w_staged = w_early;
+    if (w_early) stage_w(true);
     TZ_STAMP(PH_T1);
     tz_block_reduce3<RED_MAXU, RED_SUM, RED_SUM, 2>(nrp, sl, z0, red, rpar);
     TZ_STAMP(PH_T2);
@@ -1262,10 +1276,12 @@ retry_solve:
       if (!(nrd == nrd)) { status = 2; break; }
       if (nrd <= pi.tol_res && nrp <= pi.tol_res && mu <= pi.mu_tol) { status = 0; px_in_part = true; break; }
       if (mu <= pi.mu_floor && !fresh_warm) { status = (nrd <= pi.tol_loose && nrp <= pi.tol_loose) ? 0 : 2; px_in_part = true; break; }   // mu collapsed before the residuals: numerical
+      w_staged = false;                                // the rejected test left lambda in vin
     }
-    // Newton matrix.  is = 1/s, il = 1/lambda are the only two divisions per row and iteration.
-    TZ_ROWS(k, r) { is_[k] = tz_recip(s_[k]); il_[k] = tz_recip(l_[k]); w_[k] = l_[k] * is_[k]; vin[r] = w_[k]; }
-    __syncthreads();
+    if (!w_staged) {
+      stage_w(!w_early);
+      __syncthreads();
+    }
     TZ_STAMP(PH_TOP);
     if constexpr (TT) {                      // (the problems with at most 64 variables have shown no breakdowns: the bookkeeping costs them 0.9 %)
       if (rlev == 0 && rlev_carry != 0 && warm && (unsigned)__builtin_amdgcn_readfirstlane((int)tz_hi(mu)) <= brk_hi)
